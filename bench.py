@@ -8,6 +8,21 @@ md5hip_fill_synthetic, per-rank seed).  Per GPU: 1,048,576 x 16 KiB (C2) at
 N = 1, 2,097,152 x 16 KiB (the C4 shard: 16 M chunks over 8 GPUs) at N > 1.
 
     python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c3q|c5|crc|crcq|ctx]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: set up, W
+untimed steps, the K timed steps, the result line.  `--full` adds what else
+the benchmark measures and checks, all of it outside the timed region: the
+host-reference parity sample of the batch each rank hashed, the PMC traffic
+looked up by kernel code hash (`roofline.traffic`, `valu_busy_pmc`), the C2
+board probe, the `c3q` and `c5` sub-records of the C2 line, and the CPU
+baselines.  `--dump-outputs DIR` writes what the last timed step computed (the
+arrays a caller of the timed path receives) as DIR/<name>.npy in float32 or
+float64; inputs are seeded, so two builds can be compared output for output.
+A `--dry-run` (the CPU rehearsal of launch and aggregation) times nothing on
+a GPU and keeps its parity check either way.  The other configs' own legs
+(c3's streamed and coalesced rates, the drained rate of c3q and crcq) are
+those configs' lines and run with or without --full.
 
 N > 1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) the
 ranks are the launcher's and WORLD_SIZE must equal N.  A plain
@@ -54,6 +69,15 @@ def parse_args(argv):
                    help="untimed launches first: the board settles its clock over the first ~15 "
                         "launches of a 3 ms kernel (slow start, profiles/r01_bench_kernel_trace_startup.json)")
     p.add_argument("--config", default="c2", choices=["c2", "c3", "c3q", "c5", "crc", "crcq", "ctx"])
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline, and outside its timed region: the host-reference parity "
+                        "sample, PMC traffic by kernel code hash, the C2 board probe, the c3q / c5 "
+                        "sub-records of the C2 line and the CPU baselines (each still has its own "
+                        "switch below); a plain run sets up, warms up, times the steps and prints")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed to DIR/<name>.npy "
+                        "(float32 / float64; a fixed seeded sample of the rows of a large array, "
+                        "with the sampled rows in <name>_rows.npy)")
     p.add_argument("--chunks", type=int, default=0,
                    help="chunks per GPU (weak scaling); 0 = 1,048,576 (C2) at N=1, "
                         "2,097,152 (the C4 shard) at N>1")
@@ -204,6 +228,46 @@ def cpu_model():
     return platform.processor() or "unknown"
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES = 32 << 20          # .npy payload of one config's outputs (sampled above it)
+
+
+def dump_outputs(a, rank, world, arrays):
+    """--dump-outputs DIR: write `arrays` ({name: device tensor or numpy array,
+    first axis = chunks}: what the last timed step left for the caller) as
+    DIR/<name>.npy -- 8- and 16-bit integers as float32, 32-bit as float64,
+    both exact.  An array whose share of DUMP_BYTES would be exceeded is
+    sampled by rows: the first, the last and a seeded draw that depends only
+    on the row count, the same rows in every run, listed in <name>_rows.npy.
+    N > 1: every rank writes its own shard's as <name>_rank<r>.npy."""
+    if not a.dump_outputs:
+        return
+    import numpy as np
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    share = DUMP_BYTES // len(arrays)
+    for name, arr in arrays.items():
+        n = int(arr.shape[0])
+        wide = arr.dtype.itemsize > 2
+        row_bytes = (int(arr.numel() if hasattr(arr, "numel") else arr.size) // max(n, 1)) * (8 if wide else 4)
+        keep = max(2, share // max(row_bytes, 1))
+        rows = None
+        if n > keep:
+            draw = 1 + np.random.default_rng(0xD0C5).choice(n - 2, size=keep - 2, replace=False)
+            rows = np.sort(np.concatenate([[0, n - 1], draw])).astype(np.int64)
+            if hasattr(arr, "index_select"):
+                arr = arr.index_select(0, torch.from_numpy(rows).to(arr.device))
+            else:
+                arr = arr[rows]
+        host = arr.cpu().numpy() if hasattr(arr, "cpu") else np.asarray(arr)
+        if host.dtype == np.int32:
+            host = host.view(np.uint32)          # CRC-32 values live in int32 tensors
+        np.save(os.path.join(a.dump_outputs, f"{name}{sfx}.npy"),
+                host.astype(np.float64 if wide else np.float32))
+        if rows is not None:
+            np.save(os.path.join(a.dump_outputs, f"{name}_rows{sfx}.npy"), rows.astype(np.float64))
+
+
 # --------------------------------------------------------------------------- cpu_baseline leg
 # The host reference md5.c (oracle/_ref, built in place from /root/reference;
 # else the oracle restatement).  Timed on the C1 sample for the baseline, and
@@ -333,7 +397,10 @@ def load_traffic(path, kernel, workload):
     rocprofv3 PMC summary (profiles/traffic.json, scripts/traffic_json.py).
     Each entry carries the SHA-256 of the kernel's machine code it measured;
     unless the library's current code for that kernel has the same hash, the
-    entry is stale and traffic reads null."""
+    entry is stale and traffic reads null.  A plain run (no --full) does not
+    look it up: `path` is None."""
+    if path is None:
+        return None, "not looked up (a plain run; --full reads the PMC summary)"
     if not path or not os.path.exists(path):
         return None, "no traffic summary"
     try:
@@ -352,6 +419,8 @@ def load_traffic(path, kernel, workload):
 def load_valu_busy(path, kernel, workload):
     """VALUBusy of `kernel` on `workload` (the secondary ceiling
     beside HBM) from the same code-hash-checked PMC entry, or None."""
+    if path is None:
+        return None
     try:
         ent = json.load(open(path)).get("entries", {}).get(f"{kernel}@{workload}")
     except Exception:  # pragma: no cover
@@ -404,6 +473,7 @@ def run_dry(a, rank, world, local, device, backend):
         step()
     wall = time.perf_counter() - t0
     shard.barrier()
+    dump_outputs(a, rank, world, {"digests": out})
     wall_max = shard.max_over_ranks(wall)
     par = None
     if a.parity_sample:
@@ -457,6 +527,7 @@ def run_c2(a, rank, world, local, device, backend):
     variant = m.VARIANTS[a.variant]
     fn = lambda: m.digest_fixed(data, n, L, out=out, variant=variant)  # noqa: E731
     wall, dev_ms = timed_steps(fn, a.steps, a.warmup, world)
+    dump_outputs(a, rank, world, {"digests": out})
     wall_max = shard.max_over_ranks(wall)
     dev_ms_max = shard.max_over_ranks(dev_ms)
     value = float(n_all) * L * a.steps / wall_max / GIB
@@ -499,6 +570,7 @@ def run_crc(a, rank, world, local, device, backend):
     out = torch.empty(n, dtype=torch.int32, device="cuda")
     fn = lambda: m.crc32_fixed(data, n, L, fastcrc=F, out=out)  # noqa: E731
     wall, dev_ms = timed_steps(fn, a.steps, a.warmup, world)
+    dump_outputs(a, rank, world, {"crc32": out})
     wall_max = shard.max_over_ranks(wall)
     dev_ms_max = shard.max_over_ranks(dev_ms)
     fast = 0 < F < L
@@ -586,6 +658,7 @@ def run_crcq(a, rank, world, local, device, backend):
         drain(submit(0))
     wall_d, wall_d_max = timed(lambda: [drain(submit(0)) for _ in range(a.steps)])
     wall, wall_max = timed(pipelined)
+    dump_outputs(a, rank, world, {f"crc32_{j}": o for j, o in enumerate(outs[(a.steps - 1) & 1])})
     stats = q.stats()
     q.close()
     blocks = float(K * n)
@@ -792,6 +865,7 @@ def run_c3(a, rank, world, local, device, backend):
     out = torch.empty((lens.size, 16), dtype=torch.uint8, device="cuda")
     fn = lambda: m.digest_desc(data, d_off, d_len, d_ord, out=out, variant=dvar)  # noqa: E731
     wall, dev_ms = timed_steps(fn, a.steps, a.warmup, world)
+    dump_outputs(a, rank, world, {"digests": out})
     wall_max = shard.max_over_ranks(wall)
     payload = float(lens.sum())
     value = payload * world * a.steps / wall_max / GIB
@@ -952,6 +1026,7 @@ def run_c3q(a, rank, world, local, device, backend):
         drained_step()
     wall_d, wall_d_max = timed(lambda: [drained_step() for _ in range(a.steps)])
     wall, wall_max = timed(pipelined)
+    dump_outputs(a, rank, world, {f"digests_{j}": o for j, o in enumerate(outs[(a.steps - 1) & 1])})
     subs = [(p, L_, o) for (p, L_, _), o in zip(subs, outs[(a.steps - 1) & 1])]
     stats = q.stats()
     q.close()
@@ -1011,6 +1086,7 @@ def run_ctx(a, rank, world, local, device, backend):
     wall, dev_ms = timed_steps(fn, a.steps, a.warmup, world)
     wall_max = shard.max_over_ranks(wall)
     dev_ms_max = shard.max_over_ranks(dev_ms)
+    dump_outputs(a, rank, world, {"contexts": ctx})
     dig = m.final_ctx(ctx)
     # parity: each object hashed (warmup + steps) times its block -> the same
     # digest as MD5 over the block repeated; checked on a sample by the host reference
@@ -1089,6 +1165,7 @@ def run_c5(a, rank, world, local, device, backend):
         for _ in range(a.steps):
             dig = b.host_fixed(arr, n, L)
         wall = time.perf_counter() - t0
+    dump_outputs(a, rank, world, {"digests": dig})
     gbs = n * L * a.steps / wall / 1e9
     par = c5_sample(arr, dig, n, L, a.c5_slice // L, a.parity_sample, 55 + rank) if a.parity_sample else None
     res = {"metric": "end-to-end MD5 GiB/s from pinned host memory (C5)",
@@ -1195,6 +1272,7 @@ def run_extra(name, a, rank, world, local, device, backend):
     import copy
     b = copy.copy(a)
     b.steps, b.warmup = EXTRA_STEPS[name]
+    b.dump_outputs = None              # --dump-outputs writes the headline's outputs
     torch.cuda.empty_cache()
     t0 = time.perf_counter()
     r = {"c3q": run_c3q, "c5": run_c5}[name](b, rank, world, local, device, backend)
@@ -1213,6 +1291,11 @@ def main(argv=None):
         raise SystemExit("bench.py: --gpus must be >= 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a, argv))           # before anything touches the GPU
+    if not a.full and not a.dry_run:
+        # a plain run: set up, warm up, time the steps, print -- what else the
+        # line can carry is measured and checked under --full
+        a.parity_sample, a.extras, a.traffic = 0, "none", None
+        a.no_board_probe = a.no_cpu_baseline = True
     import torch as _torch
     torch = _torch
     sys.path.insert(0, REPO)
@@ -1237,6 +1320,7 @@ def main(argv=None):
         elif a.config == "crc":
             res["cpu_baseline"] = cpu_baseline_crc()
     if rank == 0:
+        res["full"] = bool(a.full)
         print(json.dumps(res), flush=True)
     shard.close_group()
 
