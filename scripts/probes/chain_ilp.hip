@@ -30,7 +30,7 @@ __global__ void __launch_bounds__(256) chains(uint32_t iters, uint32_t seed, uin
   for (uint32_t it = 0; it < iters; ++it) {
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      compress_regs<true, true>(st[c], w[c]);
+      compress_regs<true>(st[c], w[c]);
       // every message word depends on the chain (16 adds per compression,
       // the same for every C): no M + K is hoisted out of the loop
 #pragma unroll

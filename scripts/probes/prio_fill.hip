@@ -14,7 +14,7 @@
 using namespace md5hip;
 
 __device__ __forceinline__ void step(State& st, uint4 (&w)[4]) {
-  compress_regs<true, true>(st, w);
+  compress_regs<true>(st, w);
 #pragma unroll
   for (int q = 0; q < 4; ++q) w[q] = make_uint4(w[q].x + st.a, w[q].y + st.b, w[q].z + st.c, w[q].w + st.d);
 }

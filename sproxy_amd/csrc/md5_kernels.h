@@ -6,10 +6,10 @@
 // differs between the kernels is how message blocks travel HBM -> VGPRs:
 //
 //   md5_fixed_direct  each lane streams its own chunk with global_load_dwordx4
-//                     (4 per 64-B block), a D-deep register ring in flight.
-//   md5_fixed_lds     the wave fetches its 64 chunks' next block(s) with
-//                     LDS-DMA (global_load_lds_dwordx4: 4 or 8 lanes per chunk,
-//                     so each wave-instruction reads whole 64/128-B runs), then
+//                     (4 per 64-B block), a 2-block register ring in flight.
+//   md5_fixed_xdma1nt the wave fetches its 64 chunks' next two blocks with
+//                     LDS-DMA (buffer_load_dwordx4 ... lds: 8 lanes per chunk,
+//                     so each wave-instruction reads whole 128-B runs), then
 //                     every lane pulls its own row out of LDS with ds_read_b128.
 //                     Source-side XOR swizzle keeps the row reads conflict-free.
 //   md5_desc          per-chunk (offset, length) descriptors, optional
@@ -43,7 +43,7 @@ __device__ __forceinline__ void load_block(uint4 (&r)[4], const uint4* p) {
 // A buffer descriptor the compiler can prove wave-uniform: both address
 // halves go through readfirstlane.  Without that proof hipcc wraps every
 // buffer_load in a waterfall loop (4 v_readfirstlane + 2 v_cmp + exec juggling
-// per load; it did so in crc32_fixed_xpose, whose table setup precedes it).
+// per load; it did so in a CRC-32 kernel, whose table setup precedes it).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const uint8_t* p) {
   const uint64_t a = (uint64_t)(uintptr_t)p;
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
@@ -55,7 +55,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const uint8_t* p)
 // ---------------------------------------------------------------------------
 // Fixed-length, lane-direct loads.  base/stride 16-B aligned, len <= stride.
 // ---------------------------------------------------------------------------
-// (hashers without LDS state only: Md5Hasher, FoldHasher)
 // Ring refill.  kPair: slots are refilled two at a time (blocks 2k, 2k+1 --
 // one whole 128-B line when the chunk is 128-B aligned), so a lane never
 // leaves half a line in the cache for a later instruction: with ~16 waves x
@@ -78,18 +77,18 @@ __device__ __forceinline__ void ring_steps(H& h, typename H::State& st, uint4 (&
   }
 }
 
-template <int D, class H = Md5Hasher<false>, bool kPair = false>
 __global__ void __launch_bounds__(256)
 md5_fixed_direct(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uint64_t stride,
-                 typename H::Out* __restrict__ out) {
-  static_assert(!kPair || D % 2 == 0, "paired refill needs an even ring");
+                 uint4* __restrict__ out) {
+  using H = Md5Hasher<false>;
+  constexpr int D = 2;
   H h;
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint8_t* chunk = base + i * stride;
   const uint4* p = reinterpret_cast<const uint4*>(chunk);
   const uint32_t nfull = len >> 6;
-  typename H::State st = h.init();
+  H::State st = h.init();
   if (nfull) {
     // D-deep register ring.  Prefetch indices are clamped to the last block so
     // every load is unconditional (no phi copies); the <= D re-reads at the end
@@ -100,7 +99,7 @@ md5_fixed_direct(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uin
     for (int j = 0; j < D; ++j) load_block(R[j], p + 4 * min((uint32_t)j, lastb));
     uint32_t blk = 0;
     for (; blk + D <= nfull; blk += D)     // steady state: no conditionals, so
-      ring_steps<H, D, kPair>(h, st, R, p, blk, lastb);   // the waits stay counted
+      ring_steps<H, D, false>(h, st, R, p, blk, lastb);   // the waits stay counted
 #pragma unroll
     for (int j = 0; j < D - 1; ++j)
       if (blk + j < nfull) h.block(st, R[j]);
@@ -123,7 +122,7 @@ md5_fixed_direct(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uin
 // ---------------------------------------------------------------------------
 // xdma_group: one wave hashes the 64-chunk group starting at wave_first (< n)
 // through its 8 KiB image `img`; the hasher is set up by the caller.
-template <class H, int CP = 2>
+template <class H>
 __device__ __forceinline__ void xdma_group(H& h, const uint8_t* __restrict__ base, uint64_t n,
                                            uint32_t len, uint64_t stride, uint64_t wave_first,
                                            typename H::Out* __restrict__ out, uint8_t* img) {
@@ -143,9 +142,9 @@ __device__ __forceinline__ void xdma_group(H& h, const uint8_t* __restrict__ bas
   const uint32_t nfull = len >> 6;
   const uint32_t nstage = nfull >> 1;
   typename H::State st = h.init();
-  // CP applies to line-aligned chunks; with base or stride off the 128-B
-  // line a stage shares a line with the next, which must stay in L2: default
-  // policy (as desc_xpose_group)
+  // nt loads (cache policy 2) for line-aligned chunks; with base or stride
+  // off the 128-B line a stage shares a line with the next, which must stay
+  // in L2: default policy (as desc_xpose_group)
   const bool lined = ((((uintptr_t)base + wave_first * stride) | stride) & 127u) == 0;
   auto run = [&](auto pol) __attribute__((always_inline)) {
     constexpr int P = decltype(pol)::value;
@@ -173,8 +172,8 @@ __device__ __forceinline__ void xdma_group(H& h, const uint8_t* __restrict__ bas
     }
   };
   if (nstage) {
-    if (CP == 0 || !lined) run(std::integral_constant<int, 0>{});
-    else run(std::integral_constant<int, CP>{});
+    if (!lined) run(std::integral_constant<int, 0>{});
+    else run(std::integral_constant<int, 2>{});
   }
   // leftover odd block, then the tail
   const uint64_t i = wave_first + lane;
@@ -189,22 +188,15 @@ __device__ __forceinline__ void xdma_group(H& h, const uint8_t* __restrict__ bas
   if (lane < rows) h.store(out, i, st);
 }
 
-template <class H = Md5Hasher<false>, int CP = 2>
-__device__ __forceinline__ void fixed_xdma_body(const uint8_t* __restrict__ base, uint64_t n,
-                                                uint32_t len, uint64_t stride,
-                                                typename H::Out* __restrict__ out, uint8_t* lds) {
-  H h;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t wave_first = ((uint64_t)blockIdx.x * blockDim.x) + wave * 64u;
-  if (wave_first >= n) return;
-  xdma_group<H, CP>(h, base, n, len, stride, wave_first, out, lds + wave * 8192u);
-}
-
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5)))
 md5_fixed_xdma1nt(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uint64_t stride,
                   uint4* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t img[4 * 8192];
-  fixed_xdma_body<Md5Hasher<false>, 2>(base, n, len, stride, out, img);
+  Md5Hasher<false> h;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t wave_first = ((uint64_t)blockIdx.x * blockDim.x) + wave * 64u;
+  if (wave_first >= n) return;
+  xdma_group(h, base, n, len, stride, wave_first, out, img + wave * 8192u);
 }
 
 // ---------------------------------------------------------------------------
@@ -276,15 +268,13 @@ __device__ __forceinline__ void lane_range(H& h, typename H::State& st, const ui
 
 // kImplicit: chunk i at base + i*stride with length `flen` (the fixed-length
 // API's fallback for chunk starts that are not 16-B aligned).
-// kLat: latency-form step (md5_core.h).  kPrio: waves holding long chunks
-// raise their issue priority, so the longest serial chains -- which bound a
-// mixed batch -- progress at their latency limit while short-chunk waves fill
-// the remaining issue slots.
+// Waves holding long chunks raise their issue priority, so the longest serial
+// chains -- which bound a mixed batch -- progress at their latency limit while
+// short-chunk waves fill the remaining issue slots.
 // D: depth of the per-lane register ring (blocks in flight per lane).  Mixed
 // batches have few waves per SIMD (C3: ~1.2), so latency must be hidden by
 // prefetch depth, not by occupancy.
-template <bool kImplicit, class H = Md5Hasher<true>, bool kPrio = true, int D = 8,
-          bool kPair = false, bool kHog = false>
+template <bool kImplicit, class H, int D>
 __device__ __forceinline__ void desc_body(const uint8_t* __restrict__ base,
                                           const uint64_t* __restrict__ offs,
                                           const uint32_t* __restrict__ lens,
@@ -294,33 +284,28 @@ __device__ __forceinline__ void desc_body(const uint8_t* __restrict__ base,
                                           uint8_t* hlds = nullptr) {
   H h;
   h.setup(hlds);                     // before any early exit (may barrier)
-  if constexpr (kHog)                // claim the whole register file: one wave per SIMD
-    asm volatile("" ::: "v255", "a255");
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t c = (!kImplicit && order) ? (uint64_t)order[i] : i;
   const uint8_t* chunk = base + (kImplicit ? c * stride : offs[c]);
   const uint32_t len = kImplicit ? flen : lens[c];
   const uint32_t nfull = len >> 6;
-  if constexpr (kPrio) {
-    const uint32_t wmax = wave_max(nfull);
-    if (wmax >= 4096u) __builtin_amdgcn_s_setprio(3);        // >= 256 KiB
-    else if (wmax >= 1024u) __builtin_amdgcn_s_setprio(2);   // >= 64 KiB
-    else if (wmax >= 256u) __builtin_amdgcn_s_setprio(1);    // >= 16 KiB
-  }
+  const uint32_t wmax = wave_max(nfull);
+  if (wmax >= 4096u) __builtin_amdgcn_s_setprio(3);        // >= 256 KiB
+  else if (wmax >= 1024u) __builtin_amdgcn_s_setprio(2);   // >= 64 KiB
+  else if (wmax >= 256u) __builtin_amdgcn_s_setprio(1);    // >= 16 KiB
   typename H::State st = h.init();
-  lane_range<H, D, kPair>(h, st, chunk, len);
+  lane_range<H, D>(h, st, chunk, len);
   h.store(out, c, st);
 }
 
-template <bool kImplicit, bool kLat = true, bool kPrio = true, int D = 8, bool kPair = false,
-          bool kHog = false>
+// MD5 with the latency-form step (md5_core.h kLat) and an 8-block ring.
+template <bool kImplicit>
 __global__ void __launch_bounds__(256)
 md5_desc(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
          const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order, uint64_t n,
          uint64_t stride, uint32_t flen, uint4* __restrict__ out) {
-  desc_body<kImplicit, Md5Hasher<kLat>, kPrio, D, kPair, kHog>(base, offs, lens, order, n, stride,
-                                                               flen, out);
+  desc_body<kImplicit, Md5Hasher<true>, 8>(base, offs, lens, order, n, stride, flen, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -328,14 +313,18 @@ md5_desc(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
 // mostly full chunk_size blocks plus each object's shorter last block
 // (blk_io.c:377); lanes are ordered longest-first (md5hip_plan_order), so a
 // wave's 64 chunks have nearly equal lengths.  The wave then loads like the
-// fixed xpose kernel -- each global_load_dwordx4 wave-instruction reads 8
-// chunks x 128 B -- from per-row 64-bit addresses (chunks lie anywhere in the
+// fixed xdma kernel -- each global_load_lds_dwordx4 wave-instruction reads 8
+// chunks x 128 B straight into the wave's 8 KiB image (no VGPR staging, no
+// ds_write) -- from per-row 64-bit addresses (chunks lie anywhere in the
 // arena), a row's stage index clamped to its own last stage, and a lane
-// compresses a stage only while it still has one.  Rows without any 128-B
-// stage re-read the wave's longest chunk (always in bounds).  A wave with a
-// chunk start that is not 16-B aligned takes the lane-direct path (desc_body).
-// One wave per workgroup, as md5_desc: the dispatcher spreads long-chunk waves
-// one per CU, and s_setprio favours them.
+// compresses a stage only while it still has one.  The DMA of stage s+1 is
+// issued once this wave's row reads of stage s have returned.  Rows without
+// any 128-B stage re-read the wave's longest chunk (always in bounds).  A wave
+// with a chunk start that is not 16-B aligned takes the lane-direct path
+// (lane_range).  One wave per workgroup, as md5_desc: the dispatcher spreads
+// long-chunk waves one per CU, and s_setprio favours them.
+// desc_xpose_group: one wave hashes the 64-chunk group whose first position
+// in `order` is `first` (< n); the hasher is set up by the caller.
 // ---------------------------------------------------------------------------
 // kLong > 0: the first `nlong` waves (one per CU; with longest-first order
 // these hold the batch's longest chunks) take the lane-direct path with an
@@ -347,13 +336,7 @@ md5_desc(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
 // stage's LDS round trip (8 ds_write_b128 + 8 ds_read_b128 + waits per
 // 128 B) sits on its critical path, while one lane-direct wave per CU does
 // not yet crowd the address unit (4 per CU did: DESIGN.md §5, C3).
-// kHalf: 4 KiB half image (rows 0-31, then rows 32-63, as xpose_half_group) so
-// a hasher with large LDS tables fits beside 16 waves' images; `first` is the
-// wave's first position in `order` (< n), the hasher is set up by the caller.
-// kDma (full image, D = 1): the 8 row loads of a stage are LDS-DMA
-// (global_load_lds_dwordx4 from the same per-row addresses) straight into the
-// image, as fixed_xdma_body: no VGPR staging, no ds_write; the DMA of stage
-// s+1 is issued once this wave's row reads of stage s have returned.
+//
 // HYBRID's test that a wave's long chunks are the batch's critical path: in
 // longest-first order, the chunk `depth` positions in (two waves per CU) is at
 // most a quarter of this wave's longest.  A batch of equal-length blocks
@@ -424,13 +407,13 @@ __device__ __forceinline__ void emit(H& h, typename H::Out* __restrict__ out, ui
   }
 }
 
-// kLongPair: HYBRID's lane-direct long waves refill their 8-block ring two
-// blocks (one whole 128-B line) at a time, so no lane leaves half a line
-// behind to be fetched again after eviction (ring_steps).
-// NB (kDma): LDS-DMA images per wave, 1 or 2.  2 is BALANCED's lone wave per
+// HYBRID's lane-direct long waves refill their 8-block ring two blocks (one
+// whole 128-B line) at a time, so no lane leaves half a line behind to be
+// fetched again after eviction (ring_steps).
+// NB: LDS-DMA images per wave, 1 or 2.  2 is BALANCED's lone wave per
 // SIMD: the next stage's DMA goes into the other image under this stage's
 // row reads (below).
-// kShift (kDma, one image): a wave holding a chunk that does not start on a
+// kShift (one image): a wave holding a chunk that does not start on a
 // 128-B line loads whole LINES instead of chunk-relative 128-B stages, each
 // line once; a lane rotates its line reads by its chunk's 16-B offset s and
 // takes a window's last s pieces from the next line (one line of registers
@@ -438,8 +421,7 @@ __device__ __forceinline__ void emit(H& h, typename H::Out* __restrict__ out, ui
 // straddle two lines and share one with the next stage, which L2 evicts
 // between the two visits under 16 waves per CU (16-B-packed ragged blocks:
 // 1.29x the payload read from HBM).
-template <int CP, class H, uint32_t kLong = 0, int D = 1, bool kHalf = false, bool kPeel = true,
-          bool kDma = false, class Src = DescArrays, bool kLongPair = true, int NB = 1,
+template <int CP, class H, uint32_t kLong = 0, class Src = DescArrays, int NB = 1,
           bool kShift = false>
 __device__ __forceinline__ void desc_xpose_group(H& h, const uint8_t* __restrict__ base,
                                                  const Src& src, uint64_t n,
@@ -464,7 +446,7 @@ __device__ __forceinline__ void desc_xpose_group(H& h, const uint8_t* __restrict
   const bool unaligned = __ballot(live && (((uintptr_t)chunk & 15u) != 0)) != 0;
   if (kLong && bmax >= kLong && (first >> 6) < nlong) {
     if (live) {
-      lane_range<H, 8, kLongPair>(h, st, chunk, len);
+      lane_range<H, 8, true>(h, st, chunk, len);
       emit<Src>(h, out, c, st);
     }
     return;
@@ -494,14 +476,7 @@ __device__ __forceinline__ void desc_xpose_group(H& h, const uint8_t* __restrict
       rlast[r] = (rn ? rn : smax) - 1u;
     }
     const uint32_t g = (lane >> 1) & 7u;
-    auto load_stage = [&](u32x4 (&R)[8], uint32_t stg) __attribute__((always_inline)) {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const u32x4* a = reinterpret_cast<const u32x4*>(rptr[r] + (min(stg, rlast[r]) << 7));
-        R[r] = CP ? __builtin_nontemporal_load(a) : *a;
-      }
-    };
-    const uint8_t* myrow = img + (kHalf ? (lane & 31u) : lane) * 128u;
+    const uint8_t* myrow = img + lane * 128u;
     auto read_row = [&](uint4 (&w)[2][4]) __attribute__((always_inline)) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
@@ -509,38 +484,8 @@ __device__ __forceinline__ void desc_xpose_group(H& h, const uint8_t* __restrict
         w[q >> 2][q & 3] = make_uint4(v.x, v.y, v.z, v.w);
       }
     };
-    auto consume = [&](u32x4 (&R)[8], uint32_t stg, uint32_t next, bool refill = true)
-        __attribute__((always_inline)) {
-      uint4 w[2][4];
-      if constexpr (kHalf) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          *reinterpret_cast<u32x4*>(img + r * 1024 + lane * 16) = R[r];
-        __builtin_amdgcn_wave_barrier();
-        if (lane < 32u) read_row(w);
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int r = 4; r < 8; ++r)
-          *reinterpret_cast<u32x4*>(img + (r - 4) * 1024 + lane * 16) = R[r];
-        __builtin_amdgcn_wave_barrier();
-        if (lane >= 32u) read_row(w);
-      } else {
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-          *reinterpret_cast<u32x4*>(img + r * 1024 + lane * 16) = R[r];
-        __builtin_amdgcn_wave_barrier();
-        read_row(w);
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (refill) load_stage(R, next);
-      __builtin_amdgcn_sched_barrier(0);
-      if (stg < nst) {
-        h.block(st, w[0]);
-        h.block(st, w[1]);
-      }
-    };
-    static_assert(NB == 1 || (NB == 2 && kDma), "LDS-DMA images per wave: 1 or 2");
-    if constexpr (kDma && NB == 2) {
+    static_assert(NB == 1 || NB == 2, "LDS-DMA images per wave: 1 or 2");
+    if constexpr (NB == 2) {
       // Two 8 KiB images for a LONE wave on its SIMD (BALANCED): a lone
       // wave issues one instruction per slot, so everything it does besides
       // VALU comes straight off its chain.  Per 128-B stage: the next stage's
@@ -554,7 +499,6 @@ __device__ __forceinline__ void desc_xpose_group(H& h, const uint8_t* __restrict
       // a third image for a two-stage lead (the 96 KiB a CU already reserves
       // for BALANCED) measured 1.0-1.4 % slower on 3 and 6 coalesced C3
       // batches (profiles/r04h/balanced3_ab.json).
-      static_assert(D == 1 && !kHalf, "LDS-DMA images: full 8 KiB stages");
       const bool lined = __ballot(((uint32_t)(uintptr_t)chunk & 127u) != 0 && live && nst != 0) == 0;
       const uint32_t rmin = wave_min(nst ? nst : smax) - 1u;
       auto* limg = (__attribute__((address_space(3))) uint8_t*)img;
@@ -685,8 +629,7 @@ __device__ __forceinline__ void desc_xpose_group(H& h, const uint8_t* __restrict
       };
       if (CP == 0 || !lined) run2(std::integral_constant<int, 0>{});
       else run2(std::integral_constant<int, CP>{});
-    } else if constexpr (kDma) {
-      static_assert(D == 1 && !kHalf, "LDS-DMA image: one full 8 KiB stage");
+    } else {
       // Cache policy per wave: CP (nt for the product kernels) when every
       // row starts on a 128-B line; otherwise each 128-B stage straddles two
       // lines and shares one with the row's next stage, and nt loads let that
@@ -806,25 +749,6 @@ __device__ __forceinline__ void desc_xpose_group(H& h, const uint8_t* __restrict
       if (kShift && !lined) run_lines();
       else if (CP == 0 || !lined) run(std::integral_constant<int, 0>{});
       else run(std::integral_constant<int, CP>{});
-    } else {
-    // D-stage register ring (2*D blocks of prefetch per lane)
-    const uint32_t lasts = smax - 1;
-    u32x4 R[D][8];
-#pragma unroll
-    for (int j = 0; j < D; ++j) load_stage(R[j], min((uint32_t)j, lasts));
-    uint32_t stg = 0;
-    if constexpr (D == 1 && kPeel) {
-      for (; stg + 1 < smax; ++stg) consume(R[0], stg, stg + 1);   // last stage peeled:
-      consume(R[0], stg, 0, false);                               // no re-read past the end
-    } else {
-      for (; stg + D <= smax; stg += D) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) consume(R[j], stg + j, min(stg + j + D, lasts));
-      }
-#pragma unroll
-      for (int j = 0; j < D - 1; ++j)
-        if (stg + j < smax) consume(R[j], stg + j, lasts);
-    }
     }
   }
   if (live) {
@@ -838,18 +762,18 @@ __device__ __forceinline__ void desc_xpose_group(H& h, const uint8_t* __restrict
   }
 }
 
-template <int CP, class H = Md5Hasher<true>, uint32_t kLong = 0, int D = 1, bool kDma = false,
-          bool kShift = false>
+// The one-wave MD5 kernels' body: nt loads for line-aligned groups (CP = 2).
+template <uint32_t kLong = 0, bool kShift = false>
 __device__ __forceinline__ void desc_xpose_body(const uint8_t* __restrict__ base,
                                                 const uint64_t* __restrict__ offs,
                                                 const uint32_t* __restrict__ lens,
                                                 const uint32_t* __restrict__ order, uint64_t n,
-                                                typename H::Out* __restrict__ out, uint8_t* img,
+                                                uint4* __restrict__ out, uint8_t* img,
                                                 uint32_t nlong = 0) {
-  H h;
+  Md5Hasher<true> h;
   const uint64_t first = ((uint64_t)blockIdx.x * blockDim.x) + (threadIdx.x & ~63u);
   if (first >= n) return;
-  desc_xpose_group<CP, H, kLong, D, false, true, kDma, DescArrays, true, 1, kShift>(
+  desc_xpose_group<2, Md5Hasher<true>, kLong, DescArrays, 1, kShift>(
       h, base, DescArrays{offs, lens, order}, n, first, out, img, nlong);
 }
 
@@ -866,7 +790,7 @@ md5_desc_xdma(const uint8_t* __restrict__ base, const uint64_t* __restrict__ off
               uint4* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t img[8192];
   asm volatile("" ::: "v127");
-  desc_xpose_body<2, Md5Hasher<true>, 0, 1, true>(base, offs, lens, order, n, out, img);
+  desc_xpose_body(base, offs, lens, order, n, out, img);
 }
 
 // LINES: XDMA for batches whose chunks mostly do not start on a 128-B line
@@ -880,7 +804,7 @@ md5_desc_lines(const uint8_t* __restrict__ base, const uint64_t* __restrict__ of
                const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order, uint64_t n,
                uint4* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t img[8192];
-  desc_xpose_body<2, Md5Hasher<true>, 0, 1, true, true>(base, offs, lens, order, n, out, img);
+  desc_xpose_body<0, true>(base, offs, lens, order, n, out, img);
 }
 
 __global__ void __launch_bounds__(64)
@@ -888,8 +812,7 @@ md5_desc_hybrid(const uint8_t* __restrict__ base, const uint64_t* __restrict__ o
                 const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order, uint64_t n,
                 uint4* __restrict__ out, uint32_t nlong) {
   __shared__ __attribute__((aligned(16))) uint8_t img[8192];
-  desc_xpose_body<2, Md5Hasher<true>, kHybridLongBlocks, 1, true>(base, offs, lens, order, n, out,
-                                                                  img, nlong);   // else xdma
+  desc_xpose_body<kHybridLongBlocks>(base, offs, lens, order, n, out, img, nlong);   // else xdma
 }
 
 // ---------------------------------------------------------------------------
@@ -931,14 +854,12 @@ __device__ __forceinline__ void md5_w(const uint4 (&m)[4], uint4 (&q)[16]) {
 
 #define MD5HIP_FSTEP(F, w, x, y, z, W, s) w = x + rotl(w + (W) + F(x, y, z), s)
 
-// Steps 4*T0 .. 4*T1-1 of one block from its pre-summed addends (md5_w).  A
-// quad of steps leaves the roles (a, b, c, d) where it found them, so a block
-// can be split at any quad (the fed chain wave passes a barrier mid-block).
-template <int T0, int T1>
+// The 64 steps of one block from its pre-summed addends (md5_w), a quad of
+// steps (one uint4 of addends) per iteration.
 __device__ __forceinline__ void fed_steps(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d,
                                           const uint4 (&q)[16]) {
 #pragma unroll
-  for (int t = T0; t < T1; ++t) {
+  for (int t = 0; t < 16; ++t) {
     const uint4 v = q[t];
     if (t < 4) {
       MD5HIP_FSTEP(f1, a, b, c, d, v.x, 7);
@@ -965,16 +886,6 @@ __device__ __forceinline__ void fed_steps(uint32_t& a, uint32_t& b, uint32_t& c,
 }
 #undef MD5HIP_FSTEP
 
-// One block from its 64 pre-summed addends: MD5Transform, md5.c:63-146.
-__device__ __forceinline__ void compress_fed(State& st, const uint4 (&q)[16]) {
-  uint32_t a = st.a, b = st.b, c = st.c, d = st.d;
-  fed_steps<0, 16>(a, b, c, d, q);
-  st.a += a;  // feed-forward, md5.c:142-145
-  st.b += b;
-  st.c += c;
-  st.d += d;
-}
-
 // ---------------------------------------------------------------------------
 // Fed chains (HYBRID's long groups, two waves each).  A lone wave running 64
 // long chunks' serial chains is bound by its own VALU issue: ~20 cycles per
@@ -984,21 +895,17 @@ __device__ __forceinline__ void compress_fed(State& st, const uint4 (&q)[16]) {
 // block's 64 addends M[g(j)] + K[j] (md5_w) and hands them over through LDS
 // tables of [16 quads][64 lanes] x 16 B (both sides conflict-free); the chain
 // wave reads a block's addends with 16 ds_read_b128 and runs 4 VALU per step
-// (compress_fed).
+// (fed_steps).
 //
-// NT = 2 tables, one s_barrier per block (both waves execute 1 + bmax):
+// Two tables, one s_barrier per block (both waves execute 1 + bmax):
 //   chain : X_k | read W(k+1) from T[(k+1)&1] | block k from registers
 //   feeder: X_k | write W(k+2) into T[k&1]
 // At X_k the chain's reads of W(k) (from T[k&1], issued in iteration k-1)
 // have returned and the feeder's W(k+1) is written, so each side has a whole
-// block of slack.  NT = 1 table (16 KiB: a 2-wave workgroup then needs no more
-// LDS than two XDMA waves), two s_barriers per block (2 + 2 * bmax):
-//   chain : B_k | read W(k+1) | steps 0-15 of block k | A_k | steps 16-63
-//   feeder: B_k | A_k | write W(k+2) (under the chain's steps 16-63)  The barrier is bare (s_waitcnt lgkmcnt(0); s_barrier): a
+// block of slack.  The barrier is bare (s_waitcnt lgkmcnt(0); s_barrier): a
 // workgroup fence would also drain the feeder's global-load ring.  Lanes past
 // their own last block keep computing on whatever the feeder clamped to and
 // discard the result, so no branch ever skips a barrier.
-// kFeedOff (diagnostics): the feeder only keeps the barriers (digests wrong).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void lds_handoff() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1014,11 +921,12 @@ constexpr uint32_t kFedTable = 16 * 64 * 16;     // one block's addends, 16 KiB
 // state after the lane's nfull blocks is returned, with no padding or store.
 // kAbs: off is an absolute address (base unused; offsetting a null base would
 // be undefined), taken as a global pointer so the feeder's loads stay global.
-template <int D, int NT, bool kFeedOff = false, bool kDigest = true, bool kAbs = false>
+template <bool kDigest = true, bool kAbs = false>
 __device__ __forceinline__ State fed_long_group(const uint8_t* __restrict__ base, uint4* __restrict__ out,
                                                 uint8_t* lds, bool feeder, uint32_t nfull,
                                                 uint32_t bmax, uint64_t off, uint32_t len,
                                                 uint64_t c, bool live, State st0 = initial_state()) {
+  constexpr int D = 4;                           // the feeder's ring, refilled in pairs
   static_assert(D % 2 == 0, "paired refill");
   auto at = [&](uint64_t o) __attribute__((always_inline)) -> const uint8_t* {
     if constexpr (kAbs)
@@ -1029,7 +937,7 @@ __device__ __forceinline__ State fed_long_group(const uint8_t* __restrict__ base
   const uint8_t* chunk = at(off);
   const uint32_t lane = threadIdx.x & 63u;
   auto tab = [&](uint32_t k) __attribute__((always_inline)) {
-    return reinterpret_cast<uint4(*)[64]>(lds + (NT == 2 ? (k & 1u) * kFedTable : 0u));
+    return reinterpret_cast<uint4(*)[64]>(lds + (k & 1u) * kFedTable);
   };
   __builtin_amdgcn_s_setprio(3);
   if (feeder) {
@@ -1042,43 +950,31 @@ __device__ __forceinline__ State fed_long_group(const uint8_t* __restrict__ base
     const uint4* p = reinterpret_cast<const uint4*>(at(nfull ? off : ((uint64_t)hi << 32) | lo));
     const uint32_t lastb = (nfull ? nfull : bmax) - 1u;
     uint4 R[D][4];
-    if constexpr (!kFeedOff) {
 #pragma unroll
-      for (int j = 0; j < D; ++j) load_block(R[j], p + 4 * min((uint32_t)j, lastb));
-    }
+    for (int j = 0; j < D; ++j) load_block(R[j], p + 4 * min((uint32_t)j, lastb));
     // W(k) into T[k&1] from ring slot k % D; odd slots refill their pair
     // (blocks k-1+D, k+D: one whole 128-B line when the chunk is line-aligned)
     auto put = [&](uint32_t k, int slot) __attribute__((always_inline)) {
-      if constexpr (!kFeedOff) {
-        uint4 q[16];
-        md5_w(R[slot], q);
-        uint4 (*t)[64] = tab(k);
+      uint4 q[16];
+      md5_w(R[slot], q);
+      uint4 (*t)[64] = tab(k);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) t[i][lane] = q[i];
-        if (slot & 1) {
-          load_block(R[slot - 1], p + 4 * min(k - 1 + D, lastb));
-          load_block(R[slot], p + 4 * min(k + D, lastb));
-        }
+      for (int i = 0; i < 16; ++i) t[i][lane] = q[i];
+      if (slot & 1) {
+        load_block(R[slot - 1], p + 4 * min(k - 1 + D, lastb));
+        load_block(R[slot], p + 4 * min(k + D, lastb));
       }
     };
     put(0, 0);
-    if constexpr (NT == 1) {
-      lds_handoff();                             // B_init: W(0) in
-      lds_handoff();                             // A_init: W(0) read
-    }
     put(1, 1);
-    lds_handoff();                               // X_init / B_0: W(1) in
+    lds_handoff();                               // X_init: W(1) in
     for (uint32_t k0 = 0; k0 < bmax; k0 += D) {
 #pragma unroll
       for (int j = 0; j < D; ++j) {
         const uint32_t k = k0 + j;
         if (k < bmax) {                          // wave-uniform
-          if constexpr (NT == 1) lds_handoff();  // A_k
-          else lds_handoff();                    // X_k
+          lds_handoff();                         // X_k
           if (k + 2 < bmax) put(k + 2, (j + 2) % D);
-          if constexpr (NT == 1) {
-            if (k + 1 < bmax) lds_handoff();     // B_{k+1}
-          }
         }
       }
     }
@@ -1086,24 +982,17 @@ __device__ __forceinline__ State fed_long_group(const uint8_t* __restrict__ base
   }
   State st = st0;
   uint4 q[2][16];                                // W(k) and W(k+1), alternating
-  lds_handoff();                                 // X_init / B_init
+  lds_handoff();                                 // X_init
 #pragma unroll
   for (int i = 0; i < 16; ++i) q[0][i] = tab(0)[i][lane];
-  if constexpr (NT == 1) lds_handoff();          // A_init
   auto blk = [&](uint32_t k, uint4 (&cur)[16], uint4 (&nxt)[16]) __attribute__((always_inline)) {
     uint32_t a = st.a, b = st.b, cc = st.c, d = st.d;
-    lds_handoff(a, b, cc, d);                    // X_k / B_k
+    lds_handoff(a, b, cc, d);                    // X_k
     uint4 (*t)[64] = tab(k + 1);
 #pragma unroll
     for (int i = 0; i < 16; ++i) nxt[i] = t[i][lane];
     __builtin_amdgcn_sched_barrier(0);           // all 16 reads out before the steps
-    if constexpr (NT == 1) {
-      fed_steps<0, 4>(a, b, cc, d, cur);
-      lds_handoff(a, b, cc, d);                  // A_k: the reads of W(k+1) are in
-      fed_steps<4, 16>(a, b, cc, d, cur);
-    } else {
-      fed_steps<0, 16>(a, b, cc, d, cur);
-    }
+    fed_steps(a, b, cc, d, cur);
     const bool act = k < nfull;
     st.a = act ? st.a + a : st.a;
     st.b = act ? st.b + b : st.b;
@@ -1158,7 +1047,7 @@ md5_desc_fed(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs
   const uint32_t bmax = wave_max(nfull);
   const bool unaligned = __ballot(live && ((((uintptr_t)base + off) & 15u) != 0)) != 0;
   if (bmax >= kFedMinBlocks && !unaligned) {     // wave-uniform, the same in both waves
-    fed_long_group<4, 2>(base, out, lds, wave == 1, nfull, bmax, off, len, c, live);
+    fed_long_group(base, out, lds, wave == 1, nfull, bmax, off, len, c, live);
     return;
   }
   if (wave != 0 || !live) return;
@@ -1204,7 +1093,7 @@ struct BalancedCfg {
 // s_setprio, measured slower: a 1 MiB chain sharing its SIMD runs at half
 // speed, profiles/r02_c3_balanced_ab.json, r04v/balanced_2wps_ab.json.)
 // Returns the number of groups this wave took.
-template <int WPB, int NB, int CP = 2, uint32_t kLong = 0>
+template <int WPB, int NB, int CP>
 __device__ __forceinline__ uint32_t balanced_body(const uint8_t* __restrict__ base,
                                                   const uint64_t* __restrict__ offs,
                                                   const uint32_t* __restrict__ lens,
@@ -1224,8 +1113,8 @@ __device__ __forceinline__ uint32_t balanced_body(const uint8_t* __restrict__ ba
     t = __builtin_amdgcn_readfirstlane((uint32_t)__shfl((int)t, 0, 64));
     if ((uint64_t)t >= ngroups) break;
     ++taken;
-    desc_xpose_group<CP, Md5Hasher<true>, kLong, 1, false, true, true, DescArrays, true, NB>(
-        h, base, src, n, (uint64_t)t * 64u, out, img, 0xFFFFFFFFu);   // kLong: every long group lane-direct
+    desc_xpose_group<CP, Md5Hasher<true>, 0, DescArrays, NB>(
+        h, base, src, n, (uint64_t)t * 64u, out, img);
   }
   if (lane == 0) {
     const uint32_t total = gridDim.x * (blockDim.x >> 6);
@@ -1271,11 +1160,11 @@ md5_desc_balanced_t(const uint8_t* __restrict__ base, const uint64_t* __restrict
 // ---------------------------------------------------------------------------
 // CRC-32 batches (netcache blk_make_crc, blk_io.c:354-430), same loaders.
 // ---------------------------------------------------------------------------
-// XDMA16: the XPERM16 tables (64 KiB) beside twelve waves' full 8 KiB images
-// filled by LDS-DMA (xdma_group, as the MD5 default): no VGPR staging, no
-// ds_write, one image read per stage instead of two half-image rounds.  One
-// 768-thread workgroup per CU (160 KiB LDS), grid-stride over 64-chunk groups,
-// wave-major as crc32_xlane_body.
+// XDMA16: Crc32PermHasher's 16-copy tables (64 KiB) beside twelve waves' full
+// 8 KiB images filled by LDS-DMA (xdma_group, as the MD5 default): no VGPR
+// staging, no ds_write.  One 768-thread workgroup per CU (160 KiB LDS),
+// grid-stride over 64-chunk groups, wave-major (wave w of workgroup b starts
+// at group w * gridDim.x + b).
 __global__ void __launch_bounds__(768)
 crc32_fixed_xdma16(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uint64_t stride,
                    uint32_t* __restrict__ out) {
@@ -1286,7 +1175,7 @@ crc32_fixed_xdma16(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, u
   uint8_t* img = lds + Crc32PermHasher::kLdsBytes + wave * 8192u;
   const uint64_t ngroups = (n + 63) / 64;
   for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u)
-    xdma_group<Crc32PermHasher, 2>(h, base, n, len, stride, gi * 64u, out, img);
+    xdma_group(h, base, n, len, stride, gi * 64u, out, img);
 }
 
 // Descriptor batches with XDMA16's layout: the descriptor loader's per-row
@@ -1302,8 +1191,7 @@ crc32_desc_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__
   uint8_t* img = lds + Crc32PermHasher::kLdsBytes + wave * 8192u;
   const uint64_t ngroups = (n + 63) / 64;
   for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u)
-    desc_xpose_group<2, Crc32PermHasher, 0, 1, false, true, true>(
-        h, base, DescArrays{offs, lens, order}, n, gi * 64u, out, img);
+    desc_xpose_group<2>(h, base, DescArrays{offs, lens, order}, n, gi * 64u, out, img);
 }
 
 // fastcrc (blk_io.c:408-424) through the same LDS-DMA loader: each 64-row
@@ -1323,8 +1211,7 @@ crc32_fast_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__
   const uint64_t rows = 2 * n;
   const uint64_t ngroups = (rows + 63) / 64;
   for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u)
-    desc_xpose_group<2, Crc32PermHasher, 0, 1, false, true, true, FastWindows>(h, base, src, rows,
-                                                                               gi * 64u, out, img);
+    desc_xpose_group<2, Crc32PermHasher, 0, FastWindows>(h, base, src, rows, gi * 64u, out, img);
 }
 
 // fastcrc with F = 64 or 128 (the netcache harness runs 128): every window
@@ -1339,18 +1226,18 @@ crc32_fast_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__
 // ragged tail window) is hashed lane-direct (lane_range) with nothing in
 // flight beside it.  Persistent: one 1024-thread workgroup per CU, groups
 // wave-major, grid-stride.
-// D: window groups in flight per wave (D-1 loaded ahead of the one hashed).
-// kPairHalves: a 128-B window's two 64-B halves are requested in alternating
+// Two window groups are in flight per wave (one loaded ahead of the one
+// hashed).  A 128-B window's two 64-B halves are requested in alternating
 // instructions (bytes 0, 64, 16, 80, ...), so the second half of a line
 // reaches L2 while the first half's fill is still pending there; loaded as
 // two runs of four (0..48, then 64..112), 15 % of second halves found their
 // line already evicted and fetched it again.
-template <int D, bool kPairHalves = true>
 __device__ __forceinline__ void fast_pipe_body(const uint8_t* __restrict__ base,
                                                const uint64_t* __restrict__ offs,
                                                const uint32_t* __restrict__ lens, uint64_t n,
                                                uint64_t stride, uint32_t flen, uint32_t F,
                                                uint32_t* __restrict__ out, uint8_t* lds) {
+  constexpr int D = 2;                                    // window groups in flight per wave
   Crc32PermHasher h;
   h.setup(lds);
   const FastWindows src{offs, lens, stride, flen, F};
@@ -1378,7 +1265,7 @@ __device__ __forceinline__ void fast_pipe_body(const uint8_t* __restrict__ base,
   };
   auto fetch = [&](const Win& w, uint4 (&W)[2][4]) __attribute__((always_inline)) {
     const uint4* q = reinterpret_cast<const uint4*>(w.p);
-    if (kPairHalves && nb == 2) {
+    if (nb == 2) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {      // the barriers keep hipcc from sorting by offset
         W[0][k] = ld16(q + k);
@@ -1388,7 +1275,6 @@ __device__ __forceinline__ void fast_pipe_body(const uint8_t* __restrict__ base,
       }
     } else {
       load_block(W[0], q);
-      if (nb == 2) load_block(W[1], q + 4);
     }
   };
   auto hash = [&](const Win& w, uint64_t gi, uint4 (&W)[2][4]) __attribute__((always_inline)) {
@@ -1419,9 +1305,8 @@ __device__ __forceinline__ void fast_pipe_body(const uint8_t* __restrict__ base,
   for (;;) {
 #pragma unroll
     for (int j = 0; j < D; ++j) {
-      constexpr int kD = D;
-      const int pj = (j + kD - 1) % kD;                 // the slot freed one group ago
-      const uint64_t gp = g0 + (uint64_t)(j + kD - 1) * step;
+      const int pj = (j + D - 1) % D;                   // the slot freed one group ago
+      const uint64_t gp = g0 + (uint64_t)(j + D - 1) * step;
       win[pj] = Win{};
       if (gp < ngroups) {
         win[pj] = locate(gp);
@@ -1440,7 +1325,7 @@ crc32_fast_pipe(const uint8_t* __restrict__ base, const uint64_t* __restrict__ o
                 const uint32_t* __restrict__ lens, uint64_t n, uint64_t stride, uint32_t flen,
                 uint32_t F, uint32_t* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[Crc32PermHasher::kLdsBytes];
-  fast_pipe_body<2>(base, offs, lens, n, stride, flen, F, out, lds);
+  fast_pipe_body(base, offs, lens, n, stride, flen, F, out, lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -1528,7 +1413,7 @@ crc32_desc(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
            const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order, uint64_t n,
            uint64_t stride, uint32_t flen, uint32_t* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t tabs[Crc32Hasher::kLdsBytes];
-  desc_body<kImplicit, Crc32Hasher, true, 4>(base, offs, lens, order, n, stride, flen, out, tabs);
+  desc_body<kImplicit, Crc32Hasher, 4>(base, offs, lens, order, n, stride, flen, out, tabs);
 }
 
 // ---------------------------------------------------------------------------
@@ -1642,13 +1527,13 @@ __device__ __forceinline__ void update_ctx_body(uint32_t* __restrict__ ctxs,
   }
   const uint32_t nblk = append_only ? 0u : (len - pos) >> 6;   // md5.c:204-210
   if constexpr (kFed) {
-    st = fed_long_group<4, 2, false, false, true>(nullptr, nullptr, img, false, nblk, bmax,
-                                            (uint64_t)(uintptr_t)(data + pos), nblk << 6, 0, live, st);
+    st = fed_long_group<false, true>(nullptr, nullptr, img, false, nblk, bmax,
+                                     (uint64_t)(uintptr_t)(data + pos), nblk << 6, 0, live, st);
   } else {
     CtxHasher h;
     h.s0 = st;
     h.res = st;
-    desc_xpose_group<2, CtxHasher, 0, 1, false, true, true, LaneSpan>(
+    desc_xpose_group<2, CtxHasher, 0, LaneSpan>(
         h, nullptr, LaneSpan{(uint64_t)(uintptr_t)(data + pos), nblk << 6}, n, first, nullptr, img);
     st = h.res;
   }
@@ -1719,8 +1604,8 @@ md5_update_ctx_fed(uint32_t* __restrict__ ctxs, const uint64_t* __restrict__ ptr
     return;
   }
   if (wave == 1) {
-    fed_long_group<4, 2, false, false, true>(nullptr, nullptr, lds, true, nblk, bmax,
-                                       (uint64_t)(uintptr_t)(data + pos), nblk << 6, 0, live);
+    fed_long_group<false, true>(nullptr, nullptr, lds, true, nblk, bmax,
+                                (uint64_t)(uintptr_t)(data + pos), nblk << 6, 0, live);
     return;
   }
   update_ctx_body<true>(ctxs, ptrs, lens, n, lds, bmax);

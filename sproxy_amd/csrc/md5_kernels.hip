@@ -5,7 +5,6 @@
 namespace md5hip {
 // Explicit instantiations: kernels referenced only from host templates are
 // otherwise not emitted by hipcc (host stub and device code both missing).
-template __global__ void md5_fixed_direct<2, Md5Hasher<false>>(const uint8_t*, uint64_t, uint32_t, uint64_t, uint4*);
 template __global__ void md5_desc<false>(const uint8_t*, const uint64_t*, const uint32_t*,
                                          const uint32_t*, uint64_t, uint64_t, uint32_t, uint4*);
 template __global__ void md5_desc<true>(const uint8_t*, const uint64_t*, const uint32_t*,
@@ -284,7 +283,7 @@ int md5hip_digest_fixed_variant(const void* d_base, uint64_t n, uint32_t len, ui
   }
   // xdma1nt addresses a 64-chunk group with 32-bit buffer offsets
   if (variant == MD5HIP_DIRECT2 || stride >= (1ull << 31) / 64) {
-    hipLaunchKernelGGL((md5_fixed_direct<2, Md5Hasher<false>>), dim3((uint32_t)grid), dim3(kBlock),
+    hipLaunchKernelGGL(md5_fixed_direct, dim3((uint32_t)grid), dim3(kBlock),
                        0, s, base, n, len, stride, out);
     return launched();
   }

@@ -153,8 +153,8 @@ def test_gpu_crc_full_size(cuda):
 def test_gpu_crc_desc_netcache_blocks(cuda):
     """crc32hip_desc on the netcache shape (full blocks + ragged last blocks,
     a wave without any 128-B stage, one unaligned chunk, > one grid of
-    64-chunk groups), ordered longest-first and unordered: the XPERM16
-    descriptor kernel and its lane-direct fallback against crc32.c."""
+    64-chunk groups), ordered longest-first and unordered: the descriptor
+    kernel (crc32_desc_xdma16) and its lane-direct fallback against crc32.c."""
     import torch
     rng = np.random.default_rng(777)
     for S, n in ((4096, 40000), (65536, 700)):
