@@ -385,7 +385,9 @@ int md5_batch_submit_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
  * call returns once the chunks are staged -- the caller's buffers may be
  * reused, except in the zero-copy gather modes (registered memory is read
  * by the device until the work is done) -- and *ticket names the
- * submission (0 for an empty one).  `digests` must stay valid until
+ * submission (0 for an empty one; every entry that takes a ticket zeroes a
+ * non-NULL *ticket before it checks anything else, so it is 0 after any
+ * refused call, a NULL handle included).  `digests` must stay valid until
  * md5_batch_wait(b, ticket) returns or md5_batch_poll(b, ticket) returns 1.
  * Tickets complete independently and out of order: a ticket is done when
  * the slots holding ITS chunks are, whatever earlier tickets still run.

@@ -3,7 +3,11 @@
 #ifndef SPROXY_AMD_MD5_INTERNAL_H
 #define SPROXY_AMD_MD5_INTERNAL_H
 
+#include <errno.h>
 #include <stdint.h>
+#include <string.h>
+
+#include "../../include/md5hip.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -34,10 +38,97 @@ int md5hip_crc_desc_choice(uint64_t n, uint64_t mean_len);
 __attribute__((visibility("hidden")))
 int md5hip_lines_choice(int variant, uint64_t unlined_bytes, uint64_t bytes);
 
+/* ------------------------------------------------------------------------
+ * What a submission reads: exactly one of a flat host (ptr, len) list, page
+ * lists with per-chunk segment ranges (seg_first has one entry more than
+ * the caller has chunks, seg_first[0] = 0), device addresses (no bytes to
+ * move), or fixed-length chunks at a fixed stride from one base.  Chunk i of
+ * the source is entry first + i of the caller's arrays, so a sub-range of a
+ * caller's source is the same arrays with another `first`: nothing is copied
+ * or re-based.
+ * ------------------------------------------------------------------------ */
+enum md5hip_src_kind { MD5HIP_SRC_PTRS, MD5HIP_SRC_IOV, MD5HIP_SRC_DEVICE, MD5HIP_SRC_FIXED };
+struct md5hip_src {
+    int kind;                            /* enum md5hip_src_kind */
+    uint64_t first;
+    const void *const *ptrs;             /* PTRS */
+    const uint32_t *lens;                /* PTRS, DEVICE */
+    const struct md5hip_iov *segs;       /* IOV */
+    const uint64_t *seg_first;
+    const uint64_t *dptrs;               /* DEVICE */
+    const unsigned char *base;           /* FIXED: chunk i is (base + i * stride, len) */
+    uint32_t len;
+    uint64_t stride;
+    int base_on_device;                  /* FIXED: device memory, read in place */
+};
+
+/* 0, or -EINVAL: an array missing, a NULL pointer with a length, a seg_first
+ * that does not start at 0 or decreases, len > stride (chunks [0, n)). */
+static inline int md5hip_src_check(const struct md5hip_src *s, uint64_t n)
+{
+    const uint64_t f = s->first;
+    switch (s->kind) {
+    case MD5HIP_SRC_PTRS:
+        if (!s->ptrs || !s->lens) return -EINVAL;
+        for (uint64_t i = f; i < f + n; i++)
+            if (!s->ptrs[i] && s->lens[i]) return -EINVAL;
+        return 0;
+    case MD5HIP_SRC_DEVICE:
+        if (!s->dptrs || !s->lens) return -EINVAL;
+        for (uint64_t i = f; i < f + n; i++)
+            if (!s->dptrs[i] && s->lens[i]) return -EINVAL;
+        return 0;
+    case MD5HIP_SRC_IOV:
+        if (!s->segs || !s->seg_first || s->seg_first[0] != 0) return -EINVAL;
+        for (uint64_t i = f; i < f + n; i++) {
+            if (s->seg_first[i + 1] < s->seg_first[i]) return -EINVAL;
+            for (uint64_t j = s->seg_first[i]; j < s->seg_first[i + 1]; j++)
+                if (!s->segs[j].base && s->segs[j].len) return -EINVAL;
+        }
+        return 0;
+    case MD5HIP_SRC_FIXED:
+        return s->base && s->len <= s->stride ? 0 : -EINVAL;
+    }
+    return -EINVAL;
+}
+
+/* bytes of chunk i */
+static inline uint64_t md5hip_src_len(const struct md5hip_src *s, uint64_t i)
+{
+    if (s->kind == MD5HIP_SRC_FIXED) return s->len;
+    if (s->kind != MD5HIP_SRC_IOV) return s->lens[s->first + i];
+    uint64_t L = 0;
+    for (uint64_t j = s->seg_first[s->first + i]; j < s->seg_first[s->first + i + 1]; j++) L += s->segs[j].len;
+    return L;
+}
+
+/* digest bytes per chunk */
+static inline uint32_t md5hip_digest_size(int kind) { return kind == MD5HIP_DIGEST_CRC32 ? 4 : 16; }
+
+/* a digest kind with its fastcrc window: MD5 takes none, CRC-32's is a
+ * multiple of 4 (cfs_apix.c:2222-2236) */
+static inline int md5hip_digest_valid(int kind, uint32_t fastcrc)
+{
+    return kind == MD5HIP_DIGEST_MD5 ? fastcrc == 0 : kind == MD5HIP_DIGEST_CRC32 && (fastcrc & 3u) == 0;
+}
+
+/* verify: ok[i] = digest i of `got` equals that of `expected`; the number of
+ * mismatches */
+static inline int md5hip_verify_count(const unsigned char *got, const void *expected, uint32_t dsz, uint64_t n,
+                                      unsigned char *ok)
+{
+    const unsigned char *e = (const unsigned char *)expected;
+    int bad = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        ok[i] = memcmp(got + (size_t)dsz * i, e + (size_t)dsz * i, dsz) == 0;
+        bad += !ok[i];
+    }
+    return bad;
+}
+
 /* Batched verify with a digest kind of its own (md5_submit.c): the
  * batcher's setting is not touched, so concurrent submitters keep theirs. */
 struct md5hip_batcher;
-struct md5hip_iov;
 __attribute__((visibility("hidden")))
 int md5hip_verify_iov_as(struct md5hip_batcher *b, int kind, uint32_t fastcrc,
                          const struct md5hip_iov *segs, const uint64_t *seg_first, uint64_t n,
@@ -47,13 +138,12 @@ int md5hip_verify_iov_as(struct md5hip_batcher *b, int kind, uint32_t fastcrc,
  *   md5hip_batcher_load    weight (len + 64 per chunk) reserved in the
  *                          batcher's open and in-flight slots, read lock-free
  *   md5hip_batcher_slice   staging bytes per slot
- *   md5hip_submit_as       host chunks (ptrs/lens, or segs/seg_first when
- *                          ptrs is NULL) with an explicit digest kind;
- *                          ticket NULL = synchronous; urgent = launched at
- *                          once like a synchronous call (the caller waits
- *                          on the ticket right away)
- *   md5hip_host_fixed_as   md5hip_batch_host_fixed with an explicit kind,
- *                          optionally asynchronous
+ *   md5hip_submit_src      chunks [lo, hi) of a host source (PTRS, IOV or
+ *                          FIXED) with an explicit digest kind, digests to
+ *                          digests[0..]; ticket NULL = synchronous; urgent =
+ *                          launched at once like a synchronous call (the
+ *                          caller waits on the ticket right away; a FIXED
+ *                          source has a launch of its own either way)
  *   md5hip_batcher_ticket_state  1 done (*err = its error), 0 pending,
  *                          -EINVAL unknown; never launches anything */
 __attribute__((visibility("hidden")))
@@ -61,13 +151,8 @@ uint64_t md5hip_batcher_load(const struct md5hip_batcher *b);
 __attribute__((visibility("hidden")))
 uint64_t md5hip_batcher_slice(const struct md5hip_batcher *b);
 __attribute__((visibility("hidden")))
-int md5hip_submit_as(struct md5hip_batcher *b, int kind, uint32_t fastcrc, const void *const *ptrs,
-                     const uint32_t *lens, const struct md5hip_iov *segs, const uint64_t *seg_first,
-                     uint64_t n, unsigned char *digests, uint64_t *ticket, int urgent);
-__attribute__((visibility("hidden")))
-int md5hip_host_fixed_as(struct md5hip_batcher *b, int kind, uint32_t fastcrc, const void *h_base,
-                         uint64_t n, uint32_t len, uint64_t stride, unsigned char *digests,
-                         uint64_t *ticket);
+int md5hip_submit_src(struct md5hip_batcher *b, int kind, uint32_t fastcrc, const struct md5hip_src *src,
+                      uint64_t lo, uint64_t hi, unsigned char *digests, uint64_t *ticket, int urgent);
 __attribute__((visibility("hidden")))
 int md5hip_batcher_ticket_state(struct md5hip_batcher *b, uint64_t ticket, int *err);
 

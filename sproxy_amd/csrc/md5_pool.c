@@ -141,10 +141,7 @@ int md5hip_pool_ndev(const md5hip_pool *p) { return p ? (int)p->ndev : -EINVAL; 
 
 int md5hip_pool_set_digest(md5hip_pool *p, int kind, uint32_t fastcrc)
 {
-    if (!p) return -EINVAL;
-    if (kind == MD5HIP_DIGEST_MD5 ? fastcrc != 0
-        : kind == MD5HIP_DIGEST_CRC32 ? (fastcrc & 3u) != 0 : 1)   /* cfs_apix.c:2222-2236 */
-        return -EINVAL;
+    if (!p || !md5hip_digest_valid(kind, fastcrc)) return -EINVAL;
     pthread_mutex_lock(&p->mu);
     p->kind = kind;
     p->fastcrc = fastcrc;
@@ -356,55 +353,18 @@ static struct mt_entry *mt_find(md5hip_pool *p, uint64_t id)
 /* ------------------------------------------------------------------------
  * Submission
  * ------------------------------------------------------------------------ */
-enum src_kind { SRC_PTRS, SRC_IOV, SRC_FIXED };
-struct pool_src {
-    enum src_kind kind;
-    const void *const *ptrs;             /* SRC_PTRS */
-    const uint32_t *lens;
-    const struct md5hip_iov *segs;       /* SRC_IOV */
-    const uint64_t *seg_first;
-    const unsigned char *h_base;         /* SRC_FIXED */
-    uint32_t len;
-    uint64_t stride;
-};
-
 /* chunks [lo, hi) of `s` to device g's batcher, asynchronously; urgent =
  * the caller waits right away (launch at once, as a synchronous call) */
 static int part_submit(md5hip_pool *p, uint32_t g, int kind, uint32_t fastcrc,
-                       const struct pool_src *s, uint64_t lo, uint64_t hi, unsigned char *digests,
+                       const struct md5hip_src *s, uint64_t lo, uint64_t hi, unsigned char *digests,
                        uint64_t *ticket, int urgent)
 {
-    const uint64_t m = hi - lo;
-    switch (s->kind) {
-    case SRC_PTRS:
-        return md5hip_submit_as(p->b[g], kind, fastcrc, s->ptrs + lo, s->lens + lo, NULL, NULL, m,
-                                digests, ticket, urgent);
-    case SRC_IOV: {
-        /* the batcher reads seg_first[0..m] re-based to 0; it has taken the
-         * chunks when the call returns, so a temporary copy will do */
-        uint64_t local[65];
-        uint64_t *sf = m + 1 <= 65 ? local : malloc(8 * (m + 1));
-        if (!sf) return -ENOMEM;
-        for (uint64_t i = 0; i <= m; i++) sf[i] = s->seg_first[lo + i] - s->seg_first[lo];
-        const int rc = md5hip_submit_as(p->b[g], kind, fastcrc, NULL, NULL, s->segs + s->seg_first[lo],
-                                        sf, m, digests, ticket, urgent);
-        if (sf != local) free(sf);
-        return rc;
-    }
-    case SRC_FIXED:
-        return md5hip_host_fixed_as(p->b[g], kind, fastcrc, s->h_base + lo * s->stride, m, s->len,
-                                    s->stride, digests, ticket);
-    }
-    return -EINVAL;
+    return md5hip_submit_src(p->b[g], kind, fastcrc, s, lo, hi, digests, ticket, urgent);
 }
 
-static uint64_t src_weight(const struct pool_src *s, uint64_t i)
+static uint64_t src_weight(const struct md5hip_src *s, uint64_t i)
 {
-    if (s->kind == SRC_PTRS) return chunk_weight(s->lens[i]);
-    if (s->kind == SRC_FIXED) return chunk_weight(s->len);
-    uint64_t L = 0;
-    for (uint64_t j = s->seg_first[i]; j < s->seg_first[i + 1]; j++) L += s->segs[j].len;
-    return chunk_weight(L);
+    return chunk_weight(md5hip_src_len(s, i));
 }
 
 static void count_failover(md5hip_pool *p)
@@ -419,7 +379,7 @@ static void count_failover(md5hip_pool *p)
  * failed because its device did (the caller's buffers are still valid).
  * Either way a device that failed before taking the chunks (-ENODEV) is
  * left for another.  -ENODEV once no device is healthy. */
-static int submit_range(md5hip_pool *p, int kind, uint32_t fastcrc, const struct pool_src *s,
+static int submit_range(md5hip_pool *p, int kind, uint32_t fastcrc, const struct md5hip_src *s,
                         uint64_t lo, uint64_t hi, uint64_t w, unsigned char *digests, int sync,
                         uint32_t *g_out, uint64_t *t_out)
 {
@@ -442,12 +402,11 @@ static int submit_range(md5hip_pool *p, int kind, uint32_t fastcrc, const struct
     }
 }
 
-/* ticket NULL = synchronous; kind < 0 = the pool's current digest kind */
-static int pool_submit(md5hip_pool *p, const struct pool_src *s, uint64_t n, unsigned char *digests,
+/* n > 0 valid chunks, *ticket zeroed (pool_enter); ticket NULL =
+ * synchronous; kind < 0 = the pool's current digest kind */
+static int pool_submit(md5hip_pool *p, const struct md5hip_src *s, uint64_t n, unsigned char *digests,
                        uint64_t *ticket, int kind, uint32_t fastcrc)
 {
-    if (ticket) *ticket = 0;
-    if (n == 0) return 0;
     pthread_mutex_lock(&p->mu);
     if (kind < 0) {
         kind = p->kind;
@@ -457,10 +416,10 @@ static int pool_submit(md5hip_pool *p, const struct pool_src *s, uint64_t n, uns
     p->st.submissions++;
     pthread_mutex_unlock(&p->mu);
     if (split == 0) split = md5hip_batcher_slice(p->b[0]);
-    const uint32_t dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
+    const uint32_t dsz = md5hip_digest_size(kind);
     const int sync = ticket == NULL;
     uint64_t total = 0;
-    if (s->kind == SRC_FIXED) {
+    if (s->kind == MD5HIP_SRC_FIXED) {
         total = n * chunk_weight(s->len);
     } else {
         for (uint64_t i = 0; i < n; i++) total += src_weight(s, i);
@@ -487,7 +446,7 @@ static int pool_submit(md5hip_pool *p, const struct pool_src *s, uint64_t n, uns
     }
     /* split: contiguous byte-balanced ranges over the k least-loaded devices */
     uint64_t first[POOL_MAX_DEV + 1], w[POOL_MAX_DEV];
-    if (s->kind == SRC_FIXED) {
+    if (s->kind == MD5HIP_SRC_FIXED) {
         md5hip_pool_plan(NULL, n, k, first);
     } else {
         uint32_t *lens = malloc(4 * n);
@@ -501,7 +460,7 @@ static int pool_submit(md5hip_pool *p, const struct pool_src *s, uint64_t n, uns
     }
     for (uint32_t j = 0; j < k; j++) {
         w[j] = 0;
-        if (s->kind == SRC_FIXED) w[j] = (first[j + 1] - first[j]) * chunk_weight(s->len);
+        if (s->kind == MD5HIP_SRC_FIXED) w[j] = (first[j + 1] - first[j]) * chunk_weight(s->len);
         else for (uint64_t i = first[j]; i < first[j + 1]; i++) w[j] += src_weight(s, i);
     }
     uint32_t sel[POOL_MAX_DEV];
@@ -642,84 +601,53 @@ int md5hip_pool_poll(md5hip_pool *p, uint64_t ticket)
 /* ------------------------------------------------------------------------
  * Entries
  * ------------------------------------------------------------------------ */
-static int check_ptrs(const void *const *ptrs, const uint32_t *lens, uint64_t n)
+/* What every submit entry does once it has named its source: async = the
+ * entry has a ticket argument, which must not be NULL. */
+static int pool_enter(md5hip_pool *p, const struct md5hip_src *s, uint64_t n, unsigned char *digests,
+                      uint64_t *ticket, int async)
 {
-    if (!ptrs || !lens) return -EINVAL;
-    for (uint64_t i = 0; i < n; i++)
-        if (!ptrs[i] && lens[i]) return -EINVAL;
-    return 0;
-}
-
-static int check_iov(const struct md5hip_iov *segs, const uint64_t *seg_first, uint64_t n)
-{
-    if (!segs || !seg_first || seg_first[0] != 0) return -EINVAL;
-    for (uint64_t i = 0; i < n; i++) {
-        if (seg_first[i + 1] < seg_first[i]) return -EINVAL;
-        for (uint64_t j = seg_first[i]; j < seg_first[i + 1]; j++)
-            if (!segs[j].base && segs[j].len) return -EINVAL;
-    }
-    return 0;
+    if (ticket) *ticket = 0;
+    if (!p || (async && !ticket)) return -EINVAL;
+    if (n == 0) return 0;
+    if (!digests) return -EINVAL;
+    const int rc = md5hip_src_check(s, n);
+    return rc ? rc : pool_submit(p, s, n, digests, ticket, -1, 0);
 }
 
 int md5hip_pool_submit_async(md5hip_pool *p, const void *const *ptrs, const uint32_t *lens,
                              uint64_t n, unsigned char *digests, uint64_t *ticket)
 {
-    if (!p || !ticket) return -EINVAL;
-    *ticket = 0;
-    if (n == 0) return 0;
-    if (!digests) return -EINVAL;
-    int rc = check_ptrs(ptrs, lens, n);
-    if (rc) return rc;
-    const struct pool_src s = {SRC_PTRS, ptrs, lens, NULL, NULL, NULL, 0, 0};
-    return pool_submit(p, &s, n, digests, ticket, -1, 0);
+    const struct md5hip_src s = {.kind = MD5HIP_SRC_PTRS, .ptrs = ptrs, .lens = lens};
+    return pool_enter(p, &s, n, digests, ticket, 1);
 }
 
 int md5hip_pool_submit_iov_async(md5hip_pool *p, const struct md5hip_iov *segs,
                                  const uint64_t *seg_first, uint64_t n, unsigned char *digests,
                                  uint64_t *ticket)
 {
-    if (!p || !ticket) return -EINVAL;
-    *ticket = 0;
-    if (n == 0) return 0;
-    if (!digests) return -EINVAL;
-    int rc = check_iov(segs, seg_first, n);
-    if (rc) return rc;
-    const struct pool_src s = {SRC_IOV, NULL, NULL, segs, seg_first, NULL, 0, 0};
-    return pool_submit(p, &s, n, digests, ticket, -1, 0);
+    const struct md5hip_src s = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+    return pool_enter(p, &s, n, digests, ticket, 1);
 }
 
 int md5hip_pool_submit(md5hip_pool *p, const void *const *ptrs, const uint32_t *lens, uint64_t n,
                        unsigned char *digests)
 {
-    if (!p) return -EINVAL;
-    if (n == 0) return 0;
-    if (!digests) return -EINVAL;
-    int rc = check_ptrs(ptrs, lens, n);
-    if (rc) return rc;
-    const struct pool_src s = {SRC_PTRS, ptrs, lens, NULL, NULL, NULL, 0, 0};
-    return pool_submit(p, &s, n, digests, NULL, -1, 0);
+    const struct md5hip_src s = {.kind = MD5HIP_SRC_PTRS, .ptrs = ptrs, .lens = lens};
+    return pool_enter(p, &s, n, digests, NULL, 0);
 }
 
 int md5hip_pool_submit_iov(md5hip_pool *p, const struct md5hip_iov *segs, const uint64_t *seg_first,
                            uint64_t n, unsigned char *digests)
 {
-    if (!p) return -EINVAL;
-    if (n == 0) return 0;
-    if (!digests) return -EINVAL;
-    int rc = check_iov(segs, seg_first, n);
-    if (rc) return rc;
-    const struct pool_src s = {SRC_IOV, NULL, NULL, segs, seg_first, NULL, 0, 0};
-    return pool_submit(p, &s, n, digests, NULL, -1, 0);
+    const struct md5hip_src s = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+    return pool_enter(p, &s, n, digests, NULL, 0);
 }
 
 int md5hip_pool_host_fixed(md5hip_pool *p, const void *h_base, uint64_t n, uint32_t len,
                            uint64_t stride, unsigned char *digests)
 {
-    if (!p) return -EINVAL;
-    if (n == 0) return 0;
-    if (!h_base || !digests || len > stride) return -EINVAL;
-    const struct pool_src s = {SRC_FIXED, NULL, NULL, NULL, NULL, h_base, len, stride};
-    return pool_submit(p, &s, n, digests, NULL, -1, 0);
+    const struct md5hip_src s = {.kind = MD5HIP_SRC_FIXED, .base = h_base, .len = len, .stride = stride};
+    return pool_enter(p, &s, n, digests, NULL, 0);
 }
 
 int md5hip_pool_verify_iov(md5hip_pool *p, const struct md5hip_iov *segs, const uint64_t *seg_first,
@@ -728,25 +656,19 @@ int md5hip_pool_verify_iov(md5hip_pool *p, const struct md5hip_iov *segs, const 
     if (!p) return -EINVAL;
     if (n == 0) return 0;
     if (!expected || !ok) return -EINVAL;
-    int rc = check_iov(segs, seg_first, n);
+    const struct md5hip_src s = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+    int rc = md5hip_src_check(&s, n);
     if (rc) return rc;
     /* one snapshot of the kind for the digest size and the submission */
     pthread_mutex_lock(&p->mu);
     const int kind = p->kind;
     const uint32_t fastcrc = p->fastcrc;
     pthread_mutex_unlock(&p->mu);
-    const uint32_t dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
+    const uint32_t dsz = md5hip_digest_size(kind);
     unsigned char *got = malloc((size_t)dsz * n);
     if (!got) return -ENOMEM;
-    const struct pool_src s = {SRC_IOV, NULL, NULL, segs, seg_first, NULL, 0, 0};
     rc = pool_submit(p, &s, n, got, NULL, kind, fastcrc);
-    if (rc == 0) {
-        const unsigned char *e = expected;
-        for (uint64_t i = 0; i < n; i++) {
-            ok[i] = memcmp(got + (size_t)dsz * i, e + (size_t)dsz * i, dsz) == 0;
-            rc += !ok[i];
-        }
-    }
+    if (rc == 0) rc = md5hip_verify_count(got, expected, dsz, n, ok);
     free(got);
     return rc;
 }

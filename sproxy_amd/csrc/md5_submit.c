@@ -92,9 +92,13 @@ static long reg_find(uintptr_t p, uint64_t len)
 
 /* The caller's HIP device, restored on every exit from an entry. */
 struct dev_guard { int prev; int ok; };
-static int dev_enter(struct dev_guard *g, int device)
+static void dev_save(struct dev_guard *g)
 {
     g->ok = hipGetDevice(&g->prev) == hipSuccess;
+}
+static int dev_enter(struct dev_guard *g, int device)
+{
+    dev_save(g);
     if (hipSetDevice(device) != hipSuccess) {
         (void)hipGetLastError();      /* ours: returned as -ENODEV, not left for the caller's next check */
         if (g->ok) (void)hipSetDevice(g->prev);
@@ -115,8 +119,7 @@ int md5hip_host_register(void *base, uint64_t bytes)
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return -ENODEV;
     if (ndev > REG_MAXDEV) ndev = REG_MAXDEV;
     struct dev_guard g;
-    (void)hipGetDevice(&g.prev);
-    g.ok = 1;
+    dev_save(&g);                     /* the loop below visits every device */
     pthread_rwlock_wrlock(&g_reg_lock);
     int rc = 0;
     size_t at = 0;
@@ -269,7 +272,6 @@ struct md5hip_batcher {
     int device;
     int kind;          /* MD5HIP_DIGEST_MD5 or MD5HIP_DIGEST_CRC32 */
     uint32_t fastcrc;  /* CRC-32 head^tail window (blk_io.c:408-424), 0 = whole block */
-    uint32_t dsz;      /* digest bytes per chunk: 16 or 4 */
     uint32_t nslots;
     uint64_t cap;      /* staging bytes per slot */
     uint64_t maxn;     /* chunks per slot */
@@ -281,7 +283,7 @@ struct md5hip_batcher {
     struct slot *s;
     int open;          /* index of the OPEN slot new chunks go to, -1 = none */
     uint32_t inflight;
-    struct tk_ring tk; /* tickets: live ids, their references and errors (md5_tickets.h) */
+    struct tk_ring tk; /* tickets: live ids, their references and errors (md5_tickets.h), under mu */
     uint64_t load_bytes;      /* weight (len + 64 per chunk) reserved and not yet retired:
                                  read without the lock by md5hip_batcher_load (the pool's router) */
     struct md5hip_batcher_stats st;
@@ -335,11 +337,6 @@ static void wait_cv_us(md5hip_batcher *b, pthread_cond_t *cv, uint64_t us)
     pthread_cond_timedwait(cv, &b->mu, &ts);
 }
 static void wait_work_us(md5hip_batcher *b, uint64_t us) { wait_cv_us(b, &b->work_cv, us); }
-
-/* ticket table (md5_tickets.h), all under b->mu */
-static int tk_new(md5hip_batcher *b, uint64_t *t) { return tk_ring_new(&b->tk, t); }
-static int tk_done(const md5hip_batcher *b, uint64_t t, int *err) { return tk_ring_done(&b->tk, t, err); }
-static void tk_put(md5hip_batcher *b, uint64_t t, int err) { tk_ring_put(&b->tk, t, err); }
 
 /* One segment per (ticket, slot): a submission fills a slot until it is full
  * before it moves on, so its chunks in one slot are one contiguous run. */
@@ -579,7 +576,7 @@ static void slot_retire(md5hip_batcher *b, struct slot *sl, int err)
         const struct seg *g = &sl->segs[k];
         if (!err && !g->on_device)
             memcpy(g->user, sl->h_dig + (size_t)sl->dsz * g->first, (size_t)sl->dsz * g->count);
-        tk_put(b, g->ticket, err);
+        tk_ring_put(&b->tk, g->ticket, err);
     }
     __atomic_store_n(&b->load_bytes, b->load_bytes - sl->load, __ATOMIC_RELAXED);
     sl->load = 0;
@@ -728,7 +725,7 @@ static struct slot *slot_take(md5hip_batcher *b, int mode, int kind, uint32_t fa
             sl->mode = mode;
             sl->kind = (uint32_t)kind;
             sl->fastcrc = fastcrc;
-            sl->dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
+            sl->dsz = md5hip_digest_size(kind);
             return sl;
         }
         /* all busy: make sure the open slot can go, then wait for a retire */
@@ -769,7 +766,7 @@ static struct slot *slot_open(md5hip_batcher *b, int mode, int kind, uint32_t fa
             sl->mode = mode;
             sl->kind = (uint32_t)kind;
             sl->fastcrc = fastcrc;
-            sl->dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
+            sl->dsz = md5hip_digest_size(kind);
             b->open = (int)k;
             return sl;
         }
@@ -978,7 +975,7 @@ static void watch_launch(md5hip_batcher *b, struct slot *sl)
 static int wait_ticket(md5hip_batcher *b, uint64_t t)
 {
     int err = 0;
-    while (!tk_done(b, t, &err)) {
+    while (!tk_ring_done(&b->tk, t, &err)) {
         struct slot *in = NULL, *open = NULL;
         for (uint32_t k = 0; k < b->nslots; k++) {
             struct slot *sl = &b->s[k];
@@ -990,7 +987,7 @@ static int wait_ticket(md5hip_batcher *b, uint64_t t)
             if (sl->state == SLOT_INFLIGHT && !in) in = sl;
             else if (sl->state == SLOT_OPEN && !open) open = sl;
         }
-        if (tk_done(b, t, &err)) break;
+        if (tk_ring_done(&b->tk, t, &err)) break;
         if (in && in->watch == WATCH_NONE) {
             watch_launch(b, in);
             continue;
@@ -1084,7 +1081,6 @@ static int batcher_new(int device, uint64_t slice_bytes, uint32_t nslots, uint64
     pthread_cond_init(&b->work_cv, NULL);
     b->device = device;
     b->kind = MD5HIP_DIGEST_MD5;
-    b->dsz = 16;
     b->nslots = nslots;
     b->cap = slice_bytes;
     b->maxn = maxn;
@@ -1197,24 +1193,13 @@ static void drain(md5hip_batcher *b)
 
 int md5hip_batcher_set_digest(md5hip_batcher *b, int kind, uint32_t fastcrc)
 {
-    if (!b) return -EINVAL;
-    uint32_t dsz;
-    if (kind == MD5HIP_DIGEST_MD5) {
-        if (fastcrc) return -EINVAL;
-        dsz = 16;
-    } else if (kind == MD5HIP_DIGEST_CRC32) {
-        if (fastcrc & 3u) return -EINVAL;       /* cfs_apix.c:2222-2236 */
-        dsz = 4;
-    } else {
-        return -EINVAL;
-    }
+    if (!b || !md5hip_digest_valid(kind, fastcrc)) return -EINVAL;
     struct dev_guard g;
     if (dev_enter(&g, b->device)) return -ENODEV;  /* drain may launch the open slot */
     pthread_mutex_lock(&b->mu);
     drain(b);                                    /* never change kind under queued work */
     b->kind = kind;
     b->fastcrc = fastcrc;
-    b->dsz = dsz;
     pthread_mutex_unlock(&b->mu);
     dev_leave(&g);
     return 0;
@@ -1302,39 +1287,25 @@ int md5hip_batcher_get_stats(md5hip_batcher *b, struct md5hip_batcher_stats *out
 /* ------------------------------------------------------------------------
  * Chunk sources
  * ------------------------------------------------------------------------ */
-/* a flat (ptr, len) list, an iovec list with per-chunk segment ranges, or
- * device addresses (no bytes to move) */
-struct chunk_src {
-    const void *const *ptrs;
-    const uint32_t *lens;
-    const struct md5hip_iov *segs;
-    const uint64_t *seg_first;
-    const uint64_t *dptrs;
-};
-
-static uint64_t src_len(const struct chunk_src *s, uint64_t i)
+/* struct md5hip_src (md5_internal.h); the host kinds, PTRS and IOV, as
+ * segments: chunk i is entry s->first + i of the caller's arrays */
+static uint64_t src_nseg(const struct md5hip_src *s, uint64_t i)
 {
-    if (s->ptrs || s->dptrs) return s->lens[i];
-    uint64_t L = 0;
-    for (uint64_t j = s->seg_first[i]; j < s->seg_first[i + 1]; j++) L += s->segs[j].len;
-    return L;
+    i += s->first;
+    return s->kind == MD5HIP_SRC_PTRS ? 1 : s->seg_first[i + 1] - s->seg_first[i];
 }
 
-static uint64_t src_nseg(const struct chunk_src *s, uint64_t i)
-{
-    return s->ptrs ? 1 : s->seg_first[i + 1] - s->seg_first[i];
-}
-
-static void src_seg(const struct chunk_src *s, uint64_t i, uint64_t k, const void **base,
+static void src_seg(const struct md5hip_src *s, uint64_t i, uint64_t k, const void **base,
                     uint32_t *len)
 {
-    if (s->ptrs) { *base = s->ptrs[i]; *len = s->lens[i]; return; }
+    i += s->first;
+    if (s->kind == MD5HIP_SRC_PTRS) { *base = s->ptrs[i]; *len = s->lens[i]; return; }
     *base = s->segs[s->seg_first[i] + k].base;
     *len = s->segs[s->seg_first[i] + k].len;
 }
 
 /* Every non-empty segment of the call in registered memory? */
-static int src_registered(const struct chunk_src *s, uint64_t n)
+static int src_registered(const struct md5hip_src *s, uint64_t n)
 {
     int ok = 1;
     pthread_rwlock_rdlock(&g_reg_lock);
@@ -1349,9 +1320,10 @@ static int src_registered(const struct chunk_src *s, uint64_t n)
     return ok;
 }
 
-static void src_copy(const struct chunk_src *s, uint64_t i, unsigned char *dst)
+static void src_copy(const struct md5hip_src *s, uint64_t i, unsigned char *dst)
 {
-    if (s->ptrs) {
+    i += s->first;
+    if (s->kind == MD5HIP_SRC_PTRS) {
         if (s->lens[i]) memcpy(dst, s->ptrs[i], s->lens[i]);
         return;
     }
@@ -1362,10 +1334,11 @@ static void src_copy(const struct chunk_src *s, uint64_t i, unsigned char *dst)
 }
 
 /* Bytes [a, a + len) of chunk i to dst. */
-static void src_copy_range(const struct chunk_src *s, uint64_t i, uint64_t a, uint64_t len, unsigned char *dst)
+static void src_copy_range(const struct md5hip_src *s, uint64_t i, uint64_t a, uint64_t len, unsigned char *dst)
 {
     if (!len) return;
-    if (s->ptrs) {
+    i += s->first;
+    if (s->kind == MD5HIP_SRC_PTRS) {
         memcpy(dst, (const unsigned char *)s->ptrs[i] + a, len);
         return;
     }
@@ -1400,9 +1373,9 @@ static inline uint64_t staged_len(uint32_t F, uint64_t L) { return F && L > 2ull
 static inline uint64_t zc_pieces(uint64_t ns, int win) { return ns + (win ? 1 : 0) + 2; }
 
 /* chunk i as staged: whole, or its head and tail windows */
-static void src_copy_staged(const struct chunk_src *s, uint64_t i, uint32_t F, unsigned char *dst)
+static void src_copy_staged(const struct md5hip_src *s, uint64_t i, uint32_t F, unsigned char *dst)
 {
-    const uint64_t L = F ? src_len(s, i) : 0;
+    const uint64_t L = F ? md5hip_src_len(s, i) : 0;
     if (staged_len(F, L) == L) {
         src_copy(s, i, dst);
         return;
@@ -1411,26 +1384,11 @@ static void src_copy_staged(const struct chunk_src *s, uint64_t i, uint32_t F, u
     src_copy_range(s, i, L - F, F, dst + F);
 }
 
-/* Host gather of chunks [first, first + m) to dst + off[j].  One thread's
- * memcpy from pageable memory into pinned staging runs ~15 GB/s (DESIGN.md
- * §5), well below PCIe, so a large range is cut by bytes into parts copied
- * by MD5HIP_GATHER_THREADS threads (default 4; the calling thread copies the
- * first part). */
-struct gather_part {
-    const struct chunk_src *src;
-    uint64_t first, jlo, jhi;
-    const uint64_t *off;
-    unsigned char *dst;
-    uint32_t win;                         /* fastcrc window of a CRC-32 slot (staged_len), else 0 */
-};
-
-static void *gather_run(void *arg)
-{
-    const struct gather_part *p = arg;
-    for (uint64_t j = p->jlo; j < p->jhi; j++) src_copy_staged(p->src, p->first + j, p->win, p->dst + p->off[j]);
-    return NULL;
-}
-
+/* Large host copies are fanned out: one thread's memcpy from pageable
+ * memory into pinned staging runs ~15 GB/s, well below PCIe,
+ * so a copy past 8 MiB is cut into parts of at least 2 MiB for
+ * MD5HIP_GATHER_THREADS threads (default 4, at most 32; the calling thread
+ * takes the first part, and any part whose thread could not be created). */
 static pthread_once_t g_gather_once = PTHREAD_ONCE_INIT;
 static int g_gather_threads = 4;
 
@@ -1445,20 +1403,55 @@ static void gather_threads_init(void)
 
 #define GATHER_SPLIT_MIN (8ull << 20)   /* bytes per range before it is split */
 #define GATHER_PART_MIN (2ull << 20)    /* and at least this many bytes per part */
+enum { FAN_MAX = 32 };
 
-static void gather_range(const struct chunk_src *src, uint64_t first, uint64_t m,
-                         const uint64_t *off, unsigned char *dst, uint64_t lo, uint64_t used, uint32_t win)
+/* how many parts for `bytes` in `units` indivisible pieces: 1 .. FAN_MAX */
+static uint64_t fan_parts(uint64_t bytes, uint64_t units)
 {
     pthread_once(&g_gather_once, gather_threads_init);
-    const uint64_t bytes = used - lo;
     uint64_t T = (uint64_t)g_gather_threads;
     if (bytes < GATHER_SPLIT_MIN) T = 1;
     if (T > bytes / GATHER_PART_MIN) T = bytes / GATHER_PART_MIN ? bytes / GATHER_PART_MIN : 1;
-    if (T > m) T = m ? m : 1;
-    T = T < 1 ? 1 : T > 32 ? 32 : T;                /* the arrays below */
-    struct gather_part part[32];
-    pthread_t tid[32];
-    int started[32] = {0};
+    if (T > units) T = units ? units : 1;
+    return T < 1 ? 1 : T > FAN_MAX ? FAN_MAX : T;
+}
+
+/* run(part t) for the T <= FAN_MAX parts of `size` bytes each at `parts` */
+static void fan_out(void *(*run)(void *), void *parts, size_t size, uint64_t T)
+{
+    pthread_t tid[FAN_MAX];
+    int started[FAN_MAX] = {0};
+    for (uint64_t t = 1; t < T; t++)
+        started[t] = pthread_create(&tid[t], NULL, run, (char *)parts + t * size) == 0;
+    run(parts);
+    for (uint64_t t = 1; t < T; t++) {
+        if (started[t]) pthread_join(tid[t], NULL);
+        else run((char *)parts + t * size);      /* no thread: copy it here */
+    }
+}
+
+/* Host gather of chunks [first, first + m) to dst + off[j], the range
+ * [lo, used) of the staging cut by bytes at chunk boundaries. */
+struct gather_part {
+    const struct md5hip_src *src;
+    uint64_t first, jlo, jhi;
+    const uint64_t *off;
+    unsigned char *dst;
+    uint32_t win;                         /* fastcrc window of a CRC-32 slot (staged_len), else 0 */
+};
+
+static void *gather_run(void *arg)
+{
+    const struct gather_part *p = arg;
+    for (uint64_t j = p->jlo; j < p->jhi; j++) src_copy_staged(p->src, p->first + j, p->win, p->dst + p->off[j]);
+    return NULL;
+}
+
+static void gather_range(const struct md5hip_src *src, uint64_t first, uint64_t m,
+                         const uint64_t *off, unsigned char *dst, uint64_t lo, uint64_t used, uint32_t win)
+{
+    const uint64_t bytes = used - lo, T = fan_parts(bytes, m);
+    struct gather_part part[FAN_MAX];
     uint64_t j = 0;
     for (uint64_t t = 0; t < T; t++) {      /* part t: chunks whose offset < lo + (t+1) * bytes / T */
         const uint64_t lim = t + 1 == T ? UINT64_MAX : lo + (t + 1) * bytes / T;
@@ -1466,13 +1459,32 @@ static void gather_range(const struct chunk_src *src, uint64_t first, uint64_t m
         while (j < m && off[j] < lim) j++;
         part[t].jhi = j;
     }
-    for (uint64_t t = 1; t < T; t++)
-        started[t] = pthread_create(&tid[t], NULL, gather_run, &part[t]) == 0;
-    gather_run(&part[0]);
-    for (uint64_t t = 1; t < T; t++) {
-        if (started[t]) pthread_join(tid[t], NULL);
-        else gather_run(&part[t]);           /* no thread: copy it here */
+    fan_out(gather_run, part, sizeof part[0], T);
+}
+
+/* memcpy of `bytes`, cut evenly */
+struct copy_part {
+    unsigned char *dst;
+    const unsigned char *src;
+    uint64_t len;
+};
+
+static void *copy_run(void *arg)
+{
+    const struct copy_part *c = arg;
+    memcpy(c->dst, c->src, c->len);
+    return NULL;
+}
+
+static void copy_parallel(void *dst, const void *src, uint64_t bytes)
+{
+    const uint64_t T = fan_parts(bytes, UINT64_MAX);
+    struct copy_part part[FAN_MAX];
+    for (uint64_t t = 0; t < T; t++) {
+        const uint64_t a = bytes * t / T, z = bytes * (t + 1) / T;
+        part[t] = (struct copy_part){(unsigned char *)dst + a, (const unsigned char *)src + a, z - a};
     }
+    fan_out(copy_run, part, sizeof part[0], T);
 }
 
 /* ------------------------------------------------------------------------
@@ -1488,14 +1500,14 @@ static void gather_range(const struct chunk_src *src, uint64_t first, uint64_t m
  * profiles/r04f/) nor non-temporal stores (2.4x in isolation,
  * profiles/r04i/, no change in the submission, profiles/r04j/) shortened
  * it, so it stays one plain pass on the calling thread. */
-static void reserve_device(md5hip_batcher *b, struct slot *sl, const struct chunk_src *src, uint64_t i,
+static void reserve_device(md5hip_batcher *b, struct slot *sl, const struct md5hip_src *src, uint64_t i,
                            uint64_t m)
 {
     uint64_t *ho = sl->h_off + sl->n;
     uint32_t *hl = sl->h_len + sl->n;
     uint32_t *hh = sl->hh;
-    const uint64_t *dp = src->dptrs + i;
-    const uint32_t *ln = src->lens + i;
+    const uint64_t *dp = src->dptrs + src->first + i;
+    const uint32_t *ln = src->lens + src->first + i;
     const uint64_t dbase = (uint64_t)(uintptr_t)sl->d_data;
     uint64_t pay = 0, unl = 0;
     uint32_t last = sl->last_key, kmax = sl->hkmax;
@@ -1562,14 +1574,14 @@ static void zc_piece(struct slot *sl, int dev, const void *p, uint32_t len, long
  * staging offsets, zero-copy tables.  Returns the number reserved (the slot
  * is marked full when a chunk did not fit) or -errno.  A CRC-32 slot with a
  * fastcrc window stages each longer chunk's two windows only (staged_len). */
-static long reserve(md5hip_batcher *b, struct slot *sl, const struct chunk_src *src, uint64_t i,
+static long reserve(md5hip_batcher *b, struct slot *sl, const struct md5hip_src *src, uint64_t i,
                     uint64_t n, int zc)
 {
     const int dev = b->device;
     const uint32_t F = sl->kind == MD5HIP_DIGEST_CRC32 ? sl->fastcrc : 0;
     uint64_t j = i;
     if (sl->n == 0 && i < n) sl->opened_us = now_us();
-    if (src->dptrs) {
+    if (src->kind == MD5HIP_SRC_DEVICE) {
         const uint64_t m = n - i < b->maxn - sl->n ? n - i : b->maxn - sl->n;
         reserve_device(b, sl, src, i, m);
         if (i + m < n) sl->full = 1;
@@ -1577,7 +1589,7 @@ static long reserve(md5hip_batcher *b, struct slot *sl, const struct chunk_src *
     }
     if (zc) pthread_rwlock_rdlock(&g_reg_lock);
     while (j < n && sl->n < b->maxn) {
-        const uint64_t L = src_len(src, j);
+        const uint64_t L = md5hip_src_len(src, j);
         const uint64_t E = staged_len(F, L);
         {   /* host bytes (device-resident chunks: reserve_device above) */
             /* chunks packed on 128-B lines: the LDS-DMA loaders read 128-B
@@ -1643,6 +1655,67 @@ static long reserve(md5hip_batcher *b, struct slot *sl, const struct chunk_src *
     return (long)(j - i);
 }
 
+/* One submission between sub_begin and sub_end: the caller's device (entered
+ * by the engine before sub_begin), its ticket and its digest kind. */
+struct sub {
+    struct dev_guard g;
+    uint64_t t;
+    int kind;
+    uint32_t fastcrc, dsz;
+};
+
+/* Takes b->mu and opens the submission: the digest kind (< 0: the
+ * batcher's), a ticket, `after` checked to be a stream of this device.  On
+ * an error nothing is held any more: mu released, the caller's device put
+ * back. */
+static int sub_begin(md5hip_batcher *b, struct sub *s, int kind, uint32_t fastcrc, const hipStream_t *after)
+{
+    pthread_mutex_lock(&b->mu);
+    s->kind = kind < 0 ? b->kind : kind;
+    s->fastcrc = kind < 0 ? b->fastcrc : fastcrc;
+    s->dsz = md5hip_digest_size(s->kind);
+    s->t = 0;
+    int rc = b->failed ? b->failed : tk_ring_new(&b->tk, &s->t);
+    if (rc == 0 && after && hipEventRecord(b->after_ev, *after) != hipSuccess) {
+        tk_ring_put(&b->tk, s->t, 0);
+        rc = -EINVAL;                              /* not a stream of this device */
+    }
+    if (rc) {
+        pthread_mutex_unlock(&b->mu);
+        dev_leave(&s->g);
+        return rc;
+    }
+    b->st.submissions++;
+    return 0;
+}
+
+/* Closes the submission (mu held) with the engine's rc: drops its own
+ * reference on the ticket, hands the ticket out, waits when the call is
+ * synchronous or failed, releases mu and the device. */
+static int sub_end(md5hip_batcher *b, struct sub *s, int rc, uint64_t *ticket, int wait)
+{
+    tk_ring_put(&b->tk, s->t, rc);
+    if (ticket) *ticket = s->t;
+    if (wait || rc) {
+        const int err = wait_ticket(b, s->t);
+        if (!rc) rc = err;
+    }
+    pthread_mutex_unlock(&b->mu);
+    dev_leave(&s->g);
+    return rc;
+}
+
+/* The producer's work enqueued so far, before slot `sl`'s kernel (mu held).
+ * Recorded and waited on under one hold of b->mu -- recorded again per slot:
+ * slot_open / slot_take may have let another producer record the event
+ * meanwhile -- and before the slot's kernel can be enqueued. */
+static void slot_after(md5hip_batcher *b, struct slot *sl, const hipStream_t *after)
+{
+    if (after && (hipEventRecord(b->after_ev, *after) != hipSuccess ||
+                  hipStreamWaitEvent(sl->stream, b->after_ev, 0) != hipSuccess) && !sl->err)
+        sl->err = -EIO;
+}
+
 /* The submission engine.
  *   async   0 = synchronous (returns when the digests are delivered);
  *           1 = asynchronous (*ticket; the slot may linger and coalesce);
@@ -1655,51 +1728,34 @@ static long reserve(md5hip_batcher *b, struct slot *sl, const struct chunk_src *
  *           stream) -- every slot taking chunks of this submission waits on
  *           the producer's work enqueued so far before its kernel (an event
  *           recorded on *after, waited on by the slot's stream) */
-static int submit(md5hip_batcher *b, const struct chunk_src *src, uint64_t n, unsigned char *digests,
+static int submit(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, unsigned char *digests,
                   int on_device, int async, uint64_t *ticket, int kind, uint32_t fastcrc,
                   const hipStream_t *after)
 {
-    const int urgent = async != 1;
-    for (uint64_t i = 0; !src->dptrs && i < n; i++) {   /* device chunks: uint32 lengths, no staging */
-        const uint64_t L = src_len(src, i);
+    const int urgent = async != 1, dev_src = src->kind == MD5HIP_SRC_DEVICE;
+    for (uint64_t i = 0; !dev_src && i < n; i++) {      /* device chunks: uint32 lengths, no staging */
+        const uint64_t L = md5hip_src_len(src, i);
         if (L > 0xffffffffull) return -E2BIG;
         if ((L + 127) / 128 * 128 > b->cap) return -E2BIG;
     }
-    struct dev_guard g;
-    if (dev_enter(&g, b->device)) return -ENODEV;
+    struct sub s;
+    if (dev_enter(&s.g, b->device)) return -ENODEV;
     int zc = 0;
     /* gather is read here without mu (set_gather may change it meanwhile):
      * it only decides whether this submission may go zero-copy */
-    if (!src->dptrs && __atomic_load_n(&b->gather, __ATOMIC_RELAXED) != MD5HIP_GATHER_HOST &&
+    if (!dev_src && __atomic_load_n(&b->gather, __ATOMIC_RELAXED) != MD5HIP_GATHER_HOST &&
         b->device < REG_MAXDEV &&
         src_registered(src, n)) {
         zc = 1;
         for (uint64_t i = 0; i < n; i++)
             if (zc_pieces(src_nseg(src, i), 1) > b->segcap) zc = 0;   /* too fragmented for one table */
     }
-    const int mode = src->dptrs ? MODE_NONE : zc ? MODE_ZEROCOPY : MODE_STAGED;
-    pthread_mutex_lock(&b->mu);
-    int rc = 0;
-    uint64_t t = 0;
-    if (kind < 0) {
-        kind = b->kind;
-        fastcrc = b->fastcrc;
-    }
-    rc = b->failed ? b->failed : tk_new(b, &t);
-    if (rc == 0 && after && hipEventRecord(b->after_ev, *after) != hipSuccess) {
-        tk_put(b, t, 0);
-        rc = -EINVAL;                              /* not a stream of this device */
-    }
-    if (rc) {
-        pthread_mutex_unlock(&b->mu);
-        dev_leave(&g);
-        return rc;
-    }
-    b->st.submissions++;
-    const uint32_t dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
+    const int mode = dev_src ? MODE_NONE : zc ? MODE_ZEROCOPY : MODE_STAGED;
+    int rc = sub_begin(b, &s, kind, fastcrc, after);
+    if (rc) return rc;
     uint64_t i = 0;
     while (i < n) {
-        struct slot *sl = b->failed ? NULL : slot_open(b, mode, kind, fastcrc);
+        struct slot *sl = b->failed ? NULL : slot_open(b, mode, s.kind, s.fastcrc);
         if (!sl || b->failed) {              /* the device failed meanwhile (slot_open may wait) */
             if (sl) slot_try_launch(b, sl);  /* an empty slot it opened retires */
             rc = -ENODEV;
@@ -1722,7 +1778,7 @@ static int submit(md5hip_batcher *b, const struct chunk_src *src, uint64_t n, un
          * (a drained c3q step's 6 vectors: ~0.12 ms of copies that no longer
          * sit between the burst and its kernel); appended descriptors are
          * final, slot_prepare copies only what follows */
-        if (src->dptrs && m >= EARLY_COPY_MIN && sl->n > DESC_DIRECT_MAX && sl->n > sl->copied_n) {
+        if (dev_src && m >= EARLY_COPY_MIN && sl->n > DESC_DIRECT_MAX && sl->n > sl->copied_n) {
             const uint64_t c0 = sl->copied_n, cn = sl->n - c0;
             if (hipMemcpyAsync(sl->d_off + c0, sl->h_off + c0, 8 * cn, hipMemcpyHostToDevice, sl->stream) ||
                 hipMemcpyAsync(sl->d_len + c0, sl->h_len + c0, 4 * cn, hipMemcpyHostToDevice, sl->stream)) {
@@ -1731,18 +1787,12 @@ static int submit(md5hip_batcher *b, const struct chunk_src *src, uint64_t n, un
                 sl->copied_n = sl->n;
             }
         }
-        /* recorded and waited on under one hold of b->mu (slot_take may have
-         * let another producer record the event meanwhile), before this
-         * slot's kernel can be enqueued: the kernel runs after the producer's
-         * work enqueued up to here */
-        if (after && (hipEventRecord(b->after_ev, *after) != hipSuccess ||
-                      hipStreamWaitEvent(sl->stream, b->after_ev, 0) != hipSuccess) && !sl->err)
-            sl->err = -EIO;
-        if ((rc = seg_push(sl, (struct seg){t, at, m, digests + (size_t)dsz * i, on_device}))) {
+        slot_after(b, sl, after);
+        if ((rc = seg_push(sl, (struct seg){s.t, at, m, digests + (size_t)s.dsz * i, on_device}))) {
             sl->err = rc;                    /* its reserved chunks have no segment */
             break;
         }
-        tk_ring_ref(&b->tk, t);
+        tk_ring_ref(&b->tk, s.t);
         if (mode == MODE_STAGED && hi > lo) {
             /* copy outside the lock: other submitters may reserve behind us */
             sl->writers++;
@@ -1762,15 +1812,7 @@ static int submit(md5hip_batcher *b, const struct chunk_src *src, uint64_t n, un
         if (urgent && i >= n) sl->urgent = 1;
         slot_try_launch(b, sl);
     }
-    tk_put(b, t, rc);                        /* the submission's own reference */
-    if (ticket) *ticket = t;
-    if (!async || rc) {
-        const int err = wait_ticket(b, t);
-        if (!rc) rc = err;
-    }
-    pthread_mutex_unlock(&b->mu);
-    dev_leave(&g);
-    return rc;
+    return sub_end(b, &s, rc, ticket, !async);
 }
 
 /* A waiter or poller on `ticket` (mu held): if its chunks sit in the open
@@ -1815,7 +1857,7 @@ int md5_batch_poll(md5hip_batcher *b, uint64_t ticket)
     int rc, err = 0;
     if (ticket >= b->tk.hi) {
         rc = -EINVAL;
-    } else if (tk_done(b, ticket, &err)) {
+    } else if (tk_ring_done(&b->tk, ticket, &err)) {
         rc = err ? err : 1;
     } else {
         hasten(b, ticket);                   /* progress without the caller blocking */
@@ -1840,102 +1882,6 @@ int md5_batch_flush(md5hip_batcher *b)
     pthread_mutex_unlock(&b->mu);
     dev_leave(&g);
     return 0;
-}
-
-static int check_ptrs(const void *const *ptrs, const uint32_t *lens, uint64_t n)
-{
-    if (!ptrs || !lens) return -EINVAL;
-    for (uint64_t i = 0; i < n; i++)
-        if (!ptrs[i] && lens[i]) return -EINVAL;
-    return 0;
-}
-
-static int check_iov(const struct md5hip_iov *segs, const uint64_t *seg_first, uint64_t n)
-{
-    if (!segs || !seg_first || seg_first[0] != 0) return -EINVAL;
-    for (uint64_t i = 0; i < n; i++) {
-        if (seg_first[i + 1] < seg_first[i]) return -EINVAL;
-        for (uint64_t j = seg_first[i]; j < seg_first[i + 1]; j++)
-            if (!segs[j].base && segs[j].len) return -EINVAL;
-    }
-    return 0;
-}
-
-int md5_batch_submit(md5hip_batcher *b, const void *const *ptrs, const uint32_t *lens, uint64_t n,
-                     unsigned char *digests)
-{
-    if (!b) return -EINVAL;
-    if (n == 0) return 0;
-    if (!digests) return -EINVAL;
-    int rc = check_ptrs(ptrs, lens, n);
-    if (rc) return rc;
-    const struct chunk_src src = {ptrs, lens, NULL, NULL, NULL};
-    return submit(b, &src, n, digests, 0, 0, NULL, -1, 0, NULL);
-}
-
-int md5_batch_submit_async(md5hip_batcher *b, const void *const *ptrs, const uint32_t *lens,
-                           uint64_t n, unsigned char *digests, uint64_t *ticket)
-{
-    if (!b || !ticket) return -EINVAL;
-    *ticket = 0;                           /* an empty batch is complete at once */
-    if (n == 0) return 0;
-    if (!digests) return -EINVAL;
-    int rc = check_ptrs(ptrs, lens, n);
-    if (rc) return rc;
-    const struct chunk_src src = {ptrs, lens, NULL, NULL, NULL};
-    return submit(b, &src, n, digests, 0, 1, ticket, -1, 0, NULL);
-}
-
-int md5_batch_submit_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
-                         const uint64_t *seg_first, uint64_t n, unsigned char *digests)
-{
-    if (!b) return -EINVAL;
-    if (n == 0) return 0;
-    if (!digests) return -EINVAL;
-    int rc = check_iov(segs, seg_first, n);
-    if (rc) return rc;
-    const struct chunk_src src = {NULL, NULL, segs, seg_first, NULL};
-    return submit(b, &src, n, digests, 0, 0, NULL, -1, 0, NULL);
-}
-
-int md5_batch_submit_iov_async(md5hip_batcher *b, const struct md5hip_iov *segs,
-                               const uint64_t *seg_first, uint64_t n, unsigned char *digests,
-                               uint64_t *ticket)
-{
-    if (!b || !ticket) return -EINVAL;
-    *ticket = 0;
-    if (n == 0) return 0;
-    if (!digests) return -EINVAL;
-    int rc = check_iov(segs, seg_first, n);
-    if (rc) return rc;
-    const struct chunk_src src = {NULL, NULL, segs, seg_first, NULL};
-    return submit(b, &src, n, digests, 0, 1, ticket, -1, 0, NULL);
-}
-
-int md5_batch_submit_device_async(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
-                                  uint64_t n, unsigned char *digests, int digests_on_device,
-                                  uint64_t *ticket)
-{
-    if (!b || !ticket) return -EINVAL;
-    *ticket = 0;
-    if (n == 0) return 0;
-    if (!d_ptrs || !lens || !digests) return -EINVAL;
-    for (uint64_t i = 0; i < n; i++)
-        if (!d_ptrs[i] && lens[i]) return -EINVAL;
-    const struct chunk_src src = {NULL, lens, NULL, NULL, d_ptrs};
-    return submit(b, &src, n, digests, digests_on_device != 0, 1, ticket, -1, 0, NULL);
-}
-
-int md5_batch_submit_device(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
-                            uint64_t n, unsigned char *digests, int digests_on_device)
-{
-    if (!b) return -EINVAL;
-    if (n == 0) return 0;
-    if (!d_ptrs || !lens || !digests) return -EINVAL;
-    for (uint64_t i = 0; i < n; i++)
-        if (!d_ptrs[i] && lens[i]) return -EINVAL;
-    const struct chunk_src src = {NULL, lens, NULL, NULL, d_ptrs};
-    return submit(b, &src, n, digests, digests_on_device != 0, 0, NULL, -1, 0, NULL);
 }
 
 /* Is the byte at p page-locked host memory known to the runtime? */
@@ -1978,88 +1924,36 @@ static int host_pinned(const void *p, uint64_t len)
     return 0;
 }
 
-/* memcpy of `bytes` on MD5HIP_GATHER_THREADS threads (gather_range's rule:
- * parts of >= 2 MiB once the copy passes 8 MiB; this thread copies the
- * first part) */
-struct copy_part {
-    unsigned char *dst;
-    const unsigned char *src;
-    uint64_t len;
-};
-
-static void *copy_run(void *arg)
-{
-    const struct copy_part *c = arg;
-    memcpy(c->dst, c->src, c->len);
-    return NULL;
-}
-
-static void copy_parallel(void *dst, const void *src, uint64_t bytes)
-{
-    pthread_once(&g_gather_once, gather_threads_init);
-    uint64_t T = (uint64_t)g_gather_threads;
-    if (bytes < GATHER_SPLIT_MIN) T = 1;
-    if (T > bytes / GATHER_PART_MIN) T = bytes / GATHER_PART_MIN ? bytes / GATHER_PART_MIN : 1;
-    T = T < 1 ? 1 : T > 32 ? 32 : T;                /* the arrays below */
-    struct copy_part part[32];
-    pthread_t tid[32];
-    int started[32] = {0};
-    for (uint64_t t = 0; t < T; t++) {
-        const uint64_t a = bytes * t / T, z = bytes * (t + 1) / T;
-        part[t] = (struct copy_part){(unsigned char *)dst + a, (const unsigned char *)src + a, z - a};
-    }
-    for (uint64_t t = 1; t < T; t++) started[t] = pthread_create(&tid[t], NULL, copy_run, &part[t]) == 0;
-    copy_run(&part[0]);
-    for (uint64_t t = 1; t < T; t++) {
-        if (started[t]) pthread_join(tid[t], NULL);
-        else copy_run(&part[t]);
-    }
-}
-
-/* Fixed-length chunks from one contiguous range (MODE_FIXED), one slot per
- * slice of it: host memory (dev_src 0: one H2D copy per slot, no host
- * gather) or device memory (dev_src 1: read in place, no per-chunk
+/* Fixed-length chunks from one contiguous range (MODE_FIXED, a FIXED
+ * source), one slot per slice of it: host memory (one H2D copy per slot, no
+ * host gather) or device memory (base_on_device: read in place, no per-chunk
  * descriptor -- md5_batch_submit_device_fixed).  Digests to host memory, or
  * device memory when dig_dev.  after != NULL: the producer's stream, as
  * submit().  ticket NULL = synchronous. */
-static int fixed_submit(md5hip_batcher *b, int kind, uint32_t fastcrc, const void *base, int dev_src,
-                        uint64_t n, uint32_t len, uint64_t stride, unsigned char *digests, int dig_dev,
-                        const hipStream_t *after, uint64_t *ticket)
+static int fixed_submit(md5hip_batcher *b, int kind, uint32_t fastcrc, const struct md5hip_src *fx, uint64_t n,
+                        unsigned char *digests, int dig_dev, const hipStream_t *after, uint64_t *ticket)
 {
+    const int dev_src = fx->base_on_device;
+    const uint32_t len = fx->len;
+    const uint64_t stride = fx->stride;
     if (!dev_src && stride > b->cap) return -E2BIG;
-    struct dev_guard g;
-    if (dev_enter(&g, b->device)) return -ENODEV;
-    const unsigned char *src = (const unsigned char *)base;
+    struct sub s;
+    if (dev_enter(&s.g, b->device)) return -ENODEV;
+    const unsigned char *src = fx->base + fx->first * stride;
     uint64_t per = dev_src || !stride ? b->maxn : b->cap / stride;   /* stride 0: empty chunks */
     if (per > b->maxn) per = b->maxn;
     /* a pageable source is copied into the slot's pinned staging by this
      * thread: HIP's own pageable H2D path stalls other threads' HIP calls on
      * the device while it runs (submitters' p90 +2.7 ms beside 128 MiB
      * slices, profiles/r05f/) */
-    const int pinned = !dev_src && n && host_pinned(base, (n - 1) * stride + len);
-    pthread_mutex_lock(&b->mu);
-    if (kind < 0) {
-        kind = b->kind;
-        fastcrc = b->fastcrc;
-    }
-    const uint32_t dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
-    uint64_t t = 0;
-    int rc = b->failed ? b->failed : tk_new(b, &t);
-    if (rc == 0 && after && hipEventRecord(b->after_ev, *after) != hipSuccess) {
-        tk_put(b, t, 0);
-        rc = -EINVAL;                              /* not a stream of this device */
-    }
-    if (rc) {
-        pthread_mutex_unlock(&b->mu);
-        dev_leave(&g);
-        return rc;
-    }
-    b->st.submissions++;
+    const int pinned = !dev_src && n && host_pinned(src, (n - 1) * stride + len);
+    int rc = sub_begin(b, &s, kind, fastcrc, after);
+    if (rc) return rc;
     for (uint64_t i = 0; i < n && !rc; i += per) {
         const uint64_t m = n - i < per ? n - i : per;
         /* straight from the caller's buffer: a slot of its own (the open
          * slot keeps coalescing other work) */
-        struct slot *sl = b->failed ? NULL : slot_take(b, MODE_FIXED, kind, fastcrc);
+        struct slot *sl = b->failed ? NULL : slot_take(b, MODE_FIXED, s.kind, s.fastcrc);
         if (!sl || b->failed) {              /* the device failed (slot_take may wait) */
             if (sl) slot_retire(b, sl, -ENODEV);
             rc = -ENODEV;
@@ -2074,17 +1968,12 @@ static int fixed_submit(md5hip_batcher *b, int kind, uint32_t fastcrc, const voi
         sl->full = 1;
         sl->load = m * ((uint64_t)len + 64);
         __atomic_store_n(&b->load_bytes, b->load_bytes + sl->load, __ATOMIC_RELAXED);
-        if ((rc = seg_push(sl, (struct seg){t, 0, m, digests + (size_t)dsz * i, dig_dev}))) {
+        if ((rc = seg_push(sl, (struct seg){s.t, 0, m, digests + (size_t)s.dsz * i, dig_dev}))) {
             slot_retire(b, sl, rc);
             break;
         }
-        tk_ring_ref(&b->tk, t);
-        /* the producer's work before this call, before this slot's kernel
-         * (recorded again per slot: slot_take may have let another producer
-         * record the event meanwhile) */
-        if (after && (hipEventRecord(b->after_ev, *after) != hipSuccess ||
-                      hipStreamWaitEvent(sl->stream, b->after_ev, 0) != hipSuccess))
-            sl->err = -EIO;
+        tk_ring_ref(&b->tk, s.t);
+        slot_after(b, sl, after);            /* the slot is fresh: err == 0 */
         if (!dev_src) {
             /* the copy outside the lock, the slot held by this writer: a
              * pageable source through the pinned staging (host_pinned), a
@@ -2108,50 +1997,83 @@ static int fixed_submit(md5hip_batcher *b, int kind, uint32_t fastcrc, const voi
         }
         slot_try_launch(b, sl);
     }
-    tk_put(b, t, rc);
-    if (ticket) *ticket = t;
-    if (!ticket || rc) {
-        const int err = wait_ticket(b, t);
-        if (!rc) rc = err;
-    }
-    pthread_mutex_unlock(&b->mu);
-    dev_leave(&g);
-    return rc;
+    return sub_end(b, &s, rc, ticket, !ticket);
 }
 
-static int host_fixed(md5hip_batcher *b, int kind, uint32_t fastcrc, const void *h_base, uint64_t n,
-                      uint32_t len, uint64_t stride, unsigned char *digests, uint64_t *ticket)
-{
-    return fixed_submit(b, kind, fastcrc, h_base, 0, n, len, stride, digests, 0, NULL, ticket);
-}
-
-int md5_batch_submit_device_fixed(md5hip_batcher *b, const void *d_base, uint64_t n, uint32_t len,
-                                  uint64_t stride, unsigned char *digests, int digests_on_device,
-                                  void *producer_stream, int order, uint64_t *ticket)
+/* ------------------------------------------------------------------------
+ * Entries
+ * ------------------------------------------------------------------------ */
+/* What every submit entry does once it has named its source: the argument
+ * checks, then the engine the source goes to.  async as submit()'s: non-zero
+ * takes a ticket, which is zeroed first (an empty batch is complete at
+ * once, and no error leaves a stale ticket). */
+static int enter(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, unsigned char *digests,
+                 int on_device, int async, uint64_t *ticket, int kind, uint32_t fastcrc,
+                 const hipStream_t *after)
 {
     if (ticket) *ticket = 0;
-    if (!b) return -EINVAL;
+    if (!b || (async && !ticket)) return -EINVAL;
     if (n == 0) return 0;
-    if (!d_base || !digests || len > stride) return -EINVAL;
-    const hipStream_t after = (hipStream_t)producer_stream;
-    return fixed_submit(b, -1, 0, d_base, 1, n, len, stride, digests, digests_on_device != 0,
-                        order ? &after : NULL, ticket);
+    if (!digests) return -EINVAL;
+    const int rc = md5hip_src_check(src, n);
+    if (rc) return rc;
+    return src->kind == MD5HIP_SRC_FIXED
+               ? fixed_submit(b, kind, fastcrc, src, n, digests, on_device, after, ticket)
+               : submit(b, src, n, digests, on_device, async, ticket, kind, fastcrc, after);
+}
+
+int md5_batch_submit(md5hip_batcher *b, const void *const *ptrs, const uint32_t *lens, uint64_t n,
+                     unsigned char *digests)
+{
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_PTRS, .ptrs = ptrs, .lens = lens};
+    return enter(b, &src, n, digests, 0, 0, NULL, -1, 0, NULL);
+}
+
+int md5_batch_submit_async(md5hip_batcher *b, const void *const *ptrs, const uint32_t *lens,
+                           uint64_t n, unsigned char *digests, uint64_t *ticket)
+{
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_PTRS, .ptrs = ptrs, .lens = lens};
+    return enter(b, &src, n, digests, 0, 1, ticket, -1, 0, NULL);
+}
+
+int md5_batch_submit_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
+                         const uint64_t *seg_first, uint64_t n, unsigned char *digests)
+{
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+    return enter(b, &src, n, digests, 0, 0, NULL, -1, 0, NULL);
+}
+
+int md5_batch_submit_iov_async(md5hip_batcher *b, const struct md5hip_iov *segs,
+                               const uint64_t *seg_first, uint64_t n, unsigned char *digests,
+                               uint64_t *ticket)
+{
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+    return enter(b, &src, n, digests, 0, 1, ticket, -1, 0, NULL);
+}
+
+int md5_batch_submit_device_async(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
+                                  uint64_t n, unsigned char *digests, int digests_on_device,
+                                  uint64_t *ticket)
+{
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_DEVICE, .dptrs = d_ptrs, .lens = lens};
+    return enter(b, &src, n, digests, digests_on_device != 0, 1, ticket, -1, 0, NULL);
+}
+
+int md5_batch_submit_device(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
+                            uint64_t n, unsigned char *digests, int digests_on_device)
+{
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_DEVICE, .dptrs = d_ptrs, .lens = lens};
+    return enter(b, &src, n, digests, digests_on_device != 0, 0, NULL, -1, 0, NULL);
 }
 
 int md5_batch_submit_device_after(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
                                   uint64_t n, unsigned char *digests, int digests_on_device,
                                   void *producer_stream, int order, uint64_t *ticket)
 {
-    if (ticket) *ticket = 0;
-    if (!b) return -EINVAL;
-    if (n == 0) return 0;
-    if (!d_ptrs || !lens || !digests) return -EINVAL;
-    for (uint64_t i = 0; i < n; i++)
-        if (!d_ptrs[i] && lens[i]) return -EINVAL;
-    const struct chunk_src src = {NULL, lens, NULL, NULL, d_ptrs};
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_DEVICE, .dptrs = d_ptrs, .lens = lens};
     const hipStream_t after = (hipStream_t)producer_stream;
-    return submit(b, &src, n, digests, digests_on_device != 0, ticket != NULL, ticket, -1, 0,
-                  order ? &after : NULL);
+    return enter(b, &src, n, digests, digests_on_device != 0, ticket != NULL, ticket, -1, 0,
+                 order ? &after : NULL);
 }
 
 int md5_batch_submit_device_on(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
@@ -2162,13 +2084,22 @@ int md5_batch_submit_device_on(md5hip_batcher *b, const uint64_t *d_ptrs, const 
                                          producer_stream, producer_stream != NULL, ticket);
 }
 
+int md5_batch_submit_device_fixed(md5hip_batcher *b, const void *d_base, uint64_t n, uint32_t len,
+                                  uint64_t stride, unsigned char *digests, int digests_on_device,
+                                  void *producer_stream, int order, uint64_t *ticket)
+{
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_FIXED, .base = d_base, .len = len, .stride = stride,
+                                   .base_on_device = 1};
+    const hipStream_t after = (hipStream_t)producer_stream;
+    return enter(b, &src, n, digests, digests_on_device != 0, ticket != NULL, ticket, -1, 0,
+                 order ? &after : NULL);
+}
+
 int md5hip_batch_host_fixed(md5hip_batcher *b, const void *h_base, uint64_t n, uint32_t len,
                             uint64_t stride, unsigned char *digests)
 {
-    if (!b) return -EINVAL;
-    if (n == 0) return 0;
-    if (!h_base || !digests || len > stride) return -EINVAL;
-    return host_fixed(b, -1, 0, h_base, n, len, stride, digests, NULL);
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_FIXED, .base = h_base, .len = len, .stride = stride};
+    return enter(b, &src, n, digests, 0, 0, NULL, -1, 0, NULL);
 }
 
 /* ------------------------------------------------------------------------
@@ -2181,30 +2112,12 @@ uint64_t md5hip_batcher_load(const md5hip_batcher *b)
 
 uint64_t md5hip_batcher_slice(const md5hip_batcher *b) { return b->cap; }
 
-int md5hip_submit_as(md5hip_batcher *b, int kind, uint32_t fastcrc, const void *const *ptrs,
-                     const uint32_t *lens, const struct md5hip_iov *segs, const uint64_t *seg_first,
-                     uint64_t n, unsigned char *digests, uint64_t *ticket, int urgent)
+int md5hip_submit_src(md5hip_batcher *b, int kind, uint32_t fastcrc, const struct md5hip_src *src,
+                      uint64_t lo, uint64_t hi, unsigned char *digests, uint64_t *ticket, int urgent)
 {
-    if (ticket) *ticket = 0;
-    if (!b) return -EINVAL;
-    if (n == 0) return 0;
-    if (!digests) return -EINVAL;
-    int rc = ptrs ? check_ptrs(ptrs, lens, n) : check_iov(segs, seg_first, n);
-    if (rc) return rc;
-    const struct chunk_src src = {ptrs, ptrs ? lens : NULL, ptrs ? NULL : segs, ptrs ? NULL : seg_first,
-                                  NULL};
-    return submit(b, &src, n, digests, 0, ticket ? (urgent ? 2 : 1) : 0, ticket, kind, fastcrc, NULL);
-}
-
-int md5hip_host_fixed_as(md5hip_batcher *b, int kind, uint32_t fastcrc, const void *h_base,
-                         uint64_t n, uint32_t len, uint64_t stride, unsigned char *digests,
-                         uint64_t *ticket)
-{
-    if (ticket) *ticket = 0;
-    if (!b) return -EINVAL;
-    if (n == 0) return 0;
-    if (!h_base || !digests || len > stride) return -EINVAL;
-    return host_fixed(b, kind, fastcrc, h_base, n, len, stride, digests, ticket);
+    struct md5hip_src part = *src;
+    part.first += lo;
+    return enter(b, &part, hi - lo, digests, 0, ticket ? (urgent ? 2 : 1) : 0, ticket, kind, fastcrc, NULL);
 }
 
 int md5hip_batcher_ticket_state(md5hip_batcher *b, uint64_t ticket, int *err)
@@ -2212,7 +2125,7 @@ int md5hip_batcher_ticket_state(md5hip_batcher *b, uint64_t ticket, int *err)
     *err = 0;
     if (ticket == 0) return 1;
     pthread_mutex_lock(&b->mu);
-    int rc = ticket >= b->tk.hi ? -EINVAL : tk_done(b, ticket, err);
+    int rc = ticket >= b->tk.hi ? -EINVAL : tk_ring_done(&b->tk, ticket, err);
     pthread_mutex_unlock(&b->mu);
     return rc;
 }
@@ -2231,22 +2144,15 @@ int md5hip_verify_iov_as(md5hip_batcher *b, int kind, uint32_t fastcrc,
     if (!b) return -EINVAL;
     if (n == 0) return 0;
     if (!expected || !ok) return -EINVAL;
-    if (kind != MD5HIP_DIGEST_MD5 && kind != MD5HIP_DIGEST_CRC32) return -EINVAL;
-    if (kind == MD5HIP_DIGEST_MD5 ? fastcrc != 0 : (fastcrc & 3u) != 0) return -EINVAL;
-    int rc = check_iov(segs, seg_first, n);
+    if (!md5hip_digest_valid(kind, fastcrc)) return -EINVAL;
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+    int rc = md5hip_src_check(&src, n);
     if (rc) return rc;
-    const uint32_t dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
+    const uint32_t dsz = md5hip_digest_size(kind);
     unsigned char *got = malloc((size_t)dsz * n);
     if (!got) return -ENOMEM;
-    const struct chunk_src src = {NULL, NULL, segs, seg_first, NULL};
     rc = submit(b, &src, n, got, 0, 0, NULL, kind, fastcrc, NULL);
-    if (rc == 0) {
-        const unsigned char *e = (const unsigned char *)expected;
-        for (uint64_t i = 0; i < n; i++) {
-            ok[i] = memcmp(got + (size_t)dsz * i, e + (size_t)dsz * i, dsz) == 0;
-            rc += !ok[i];
-        }
-    }
+    if (rc == 0) rc = md5hip_verify_count(got, expected, dsz, n, ok);
     free(got);
     return rc;
 }

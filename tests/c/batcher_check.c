@@ -18,7 +18,13 @@
  * stream's (fake_hip_wrong_device stays 0): waits and polls on another
  * device's ticket included.
  *
- * Before that, the blocked-caller phase: 64 threads wait on tickets that all
+ * First of all, arguments(): every public submit and verify entry called
+ * with one argument wrong (NULL handle, ticket, digests or source array, a
+ * NULL pointer with a length, a seg_first that does not start at 0 or
+ * decreases, len > stride) returns -EINVAL, or 0 for n == 0, and zeroes
+ * *ticket.
+ *
+ * Before the threads, the blocked-caller phase: 64 threads wait on tickets that all
  * sit in ONE open slot behind a held launch; when the launch is released the
  * slot goes in flight, one of them watches it, and (every other round) that
  * watcher's spin ends on NotReady just as the kernel finishes and the
@@ -34,7 +40,8 @@
  * moves a synchronous submission off the failed device and never routes to
  * it again; 8 threads at once while a device dies under them.  Then
  * fragmented(): chunks of ~4,096 one-byte registered segments, at the edge of
- * a slot's zero-copy table, MD5 and fastcrc.
+ * a slot's zero-copy table, MD5 and fastcrc.  Then pool_split_iov(): page
+ * lists the pool splits three ways, the later parts starting mid-list.
  * Exits 0 when every check holds.
  */
 #include <errno.h>
@@ -933,6 +940,264 @@ static int partly_pinned(void)
     return bad;
 }
 
+/* A page-list submission the pool splits three ways, more than 64 chunks of
+ * 1 to 3 segments per part, so the second and third part start in the middle of
+ * the caller's segs / seg_first (each batcher reads them in place, from its
+ * part's first chunk on): staged from pageable memory and zero-copy from
+ * registered memory, as MD5 and as CRC-32 with a fastcrc window shorter than
+ * every chunk, synchronous and asynchronous. */
+static int pool_split_iov(void)
+{
+    enum { N = 300, FW = 100 };
+    const int devs[3] = {0, 1, 2};
+    md5hip_pool *p;
+    int rc = md5hip_pool_create(devs, 3, 1u << 20, 2, &p);
+    if (rc) { printf("FAIL split iov pool %d\n", rc); return 1; }
+    md5hip_pool_set_split(p, 16u << 10);
+    static struct md5hip_iov segs[3 * N];
+    static uint64_t first[N + 1];
+    static int idx[N];
+    static unsigned char dig[N][16];
+    static uint32_t crc[N], lens[N];
+    uint64_t s = 0xD1CE, weight = 0;
+    for (int i = 0; i < N; i++) {
+        do idx[i] = (int)(rnd(&s) % NCH); while (g_lens[idx[i]] <= 2 * FW || g_lens[idx[i]] > 3000);
+        lens[i] = g_lens[idx[i]];
+        weight += lens[i] + 64u;
+    }
+    uint64_t cut[4];
+    md5hip_pool_plan(lens, N, 3, cut);                  /* the pool's own byte balance */
+    int bad = 0;
+    for (int g = 0; g < 3; g++)
+        if (cut[g + 1] - cut[g] <= 64) {
+            printf("FAIL split page lists: part %d has %llu chunks\n", g, (unsigned long long)(cut[g + 1] - cut[g]));
+            bad = 1;
+        }
+    for (int run = 0; run < 4 && !bad; run++) {
+        const unsigned char *mem = run & 1 ? g_heap : g_pageable;      /* registered / staged */
+        const int as_crc = run >= 2;
+        uint64_t ns = 0;
+        for (int i = 0; i < N; i++) {
+            const unsigned char *c = mem + g_offs[idx[i]];
+            const uint32_t L = g_lens[idx[i]], k = 1 + (uint32_t)i % 3, a = L / k;
+            first[i] = ns;
+            for (uint32_t q = 0; q < k; q++)
+                segs[ns++] = (struct md5hip_iov){c + q * a, q + 1 == k ? L - q * a : a};
+        }
+        first[N] = ns;
+        rc = md5hip_pool_set_digest(p, as_crc ? MD5HIP_DIGEST_CRC32 : MD5HIP_DIGEST_MD5, as_crc ? FW : 0);
+        unsigned char *out = as_crc ? (unsigned char *)crc : &dig[0][0];
+        memset(out, 0, as_crc ? sizeof crc : sizeof dig);
+        struct md5hip_pool_stats st0, st1;
+        md5hip_pool_get_stats(p, &st0);
+        if (!rc && run % 3 == 0) {
+            rc = md5hip_pool_submit_iov(p, segs, first, N, out);
+        } else if (!rc) {
+            uint64_t tk = 0;
+            rc = md5hip_pool_submit_iov_async(p, segs, first, N, out, &tk);
+            if (!rc && !(tk >> 63)) rc = -5000;                        /* a split ticket */
+            if (!rc) rc = md5hip_pool_wait(p, tk);
+        }
+        md5hip_pool_get_stats(p, &st1);
+        for (int i = 0; i < N && !rc; i++) {
+            const unsigned char *c = g_heap + g_offs[idx[i]];
+            const uint32_t L = g_lens[idx[i]];
+            if (as_crc ? crc[i] != (nc_crc32(c, FW) ^ nc_crc32(c + L - FW, FW)) : memcmp(dig[i], g_md5[idx[i]], 16) != 0)
+                rc = -5100 - i;
+        }
+        if (rc || st1.split != st0.split + 1 || st1.parts != st0.parts + 3) {
+            printf("FAIL split page lists, %s %s: rc %d, %llu split into %llu parts (weight %llu)\n",
+                   run & 1 ? "registered" : "staged", as_crc ? "fastcrc" : "md5", rc,
+                   (unsigned long long)(st1.split - st0.split), (unsigned long long)(st1.parts - st0.parts),
+                   (unsigned long long)weight);
+            bad = 1;
+        }
+    }
+    md5hip_pool_destroy(p);
+    if (!bad) printf("split page lists: 3 parts of more than 64 chunks read in place, staged and registered, md5 and fastcrc ok\n");
+    return bad;
+}
+
+/* ---------------------------------------------------------------- arguments */
+/* Every public submit entry, the two verify entries and
+ * md5_batch_submit_device_fixed, each called with one argument wrong and the
+ * rest valid: the return code and what is left in *ticket (preset to a
+ * sentinel).  No call gets as far as the device. */
+enum arg_shape { SH_PTRS, SH_IOV, SH_DEV, SH_FIXED };
+enum arg_ticket { TK_NONE, TK_REQUIRED, TK_OPTIONAL };
+enum arg_entry {
+    E_SUBMIT, E_SUBMIT_ASYNC, E_IOV, E_IOV_ASYNC, E_DEVICE, E_DEVICE_ASYNC, E_DEVICE_ON, E_DEVICE_AFTER,
+    E_HOST_FIXED, E_DEVICE_FIXED, E_VERIFY, E_POOL, E_POOL_ASYNC, E_POOL_IOV, E_POOL_IOV_ASYNC,
+    E_POOL_FIXED, E_POOL_VERIFY, E_COUNT
+};
+static const struct {
+    const char *name;
+    int shape, ticket, pool, verify;
+} g_entries[E_COUNT] = {
+    [E_SUBMIT] = {"md5_batch_submit", SH_PTRS, TK_NONE, 0, 0},
+    [E_SUBMIT_ASYNC] = {"md5_batch_submit_async", SH_PTRS, TK_REQUIRED, 0, 0},
+    [E_IOV] = {"md5_batch_submit_iov", SH_IOV, TK_NONE, 0, 0},
+    [E_IOV_ASYNC] = {"md5_batch_submit_iov_async", SH_IOV, TK_REQUIRED, 0, 0},
+    [E_DEVICE] = {"md5_batch_submit_device", SH_DEV, TK_NONE, 0, 0},
+    [E_DEVICE_ASYNC] = {"md5_batch_submit_device_async", SH_DEV, TK_REQUIRED, 0, 0},
+    [E_DEVICE_ON] = {"md5_batch_submit_device_on", SH_DEV, TK_OPTIONAL, 0, 0},
+    [E_DEVICE_AFTER] = {"md5_batch_submit_device_after", SH_DEV, TK_OPTIONAL, 0, 0},
+    [E_HOST_FIXED] = {"md5hip_batch_host_fixed", SH_FIXED, TK_NONE, 0, 0},
+    [E_DEVICE_FIXED] = {"md5_batch_submit_device_fixed", SH_FIXED, TK_OPTIONAL, 0, 0},
+    [E_VERIFY] = {"md5hip_batch_verify_iov", SH_IOV, TK_NONE, 0, 1},
+    [E_POOL] = {"md5hip_pool_submit", SH_PTRS, TK_NONE, 1, 0},
+    [E_POOL_ASYNC] = {"md5hip_pool_submit_async", SH_PTRS, TK_REQUIRED, 1, 0},
+    [E_POOL_IOV] = {"md5hip_pool_submit_iov", SH_IOV, TK_NONE, 1, 0},
+    [E_POOL_IOV_ASYNC] = {"md5hip_pool_submit_iov_async", SH_IOV, TK_REQUIRED, 1, 0},
+    [E_POOL_FIXED] = {"md5hip_pool_host_fixed", SH_FIXED, TK_NONE, 1, 0},
+    [E_POOL_VERIFY] = {"md5hip_pool_verify_iov", SH_IOV, TK_NONE, 1, 1},
+};
+
+struct arg_set {
+    void *h;                              /* batcher or pool */
+    const void *const *ptrs;
+    const uint32_t *lens;
+    const uint64_t *dptrs;
+    const struct md5hip_iov *segs;
+    const uint64_t *first;
+    const void *base;
+    uint32_t len;
+    uint64_t stride, n;
+    unsigned char *dig, *ok;              /* dig: digests out, or a verify's expected */
+    uint64_t *tk;
+};
+
+static int arg_call(int e, const struct arg_set *a)
+{
+    md5hip_batcher *b = a->h;
+    md5hip_pool *p = a->h;
+    switch (e) {
+    case E_SUBMIT: return md5_batch_submit(b, a->ptrs, a->lens, a->n, a->dig);
+    case E_SUBMIT_ASYNC: return md5_batch_submit_async(b, a->ptrs, a->lens, a->n, a->dig, a->tk);
+    case E_IOV: return md5_batch_submit_iov(b, a->segs, a->first, a->n, a->dig);
+    case E_IOV_ASYNC: return md5_batch_submit_iov_async(b, a->segs, a->first, a->n, a->dig, a->tk);
+    case E_DEVICE: return md5_batch_submit_device(b, a->dptrs, a->lens, a->n, a->dig, 0);
+    case E_DEVICE_ASYNC: return md5_batch_submit_device_async(b, a->dptrs, a->lens, a->n, a->dig, 0, a->tk);
+    case E_DEVICE_ON: return md5_batch_submit_device_on(b, a->dptrs, a->lens, a->n, a->dig, 0, NULL, a->tk);
+    case E_DEVICE_AFTER:
+        return md5_batch_submit_device_after(b, a->dptrs, a->lens, a->n, a->dig, 0, NULL, 0, a->tk);
+    case E_HOST_FIXED: return md5hip_batch_host_fixed(b, a->base, a->n, a->len, a->stride, a->dig);
+    case E_DEVICE_FIXED:
+        return md5_batch_submit_device_fixed(b, a->base, a->n, a->len, a->stride, a->dig, 0, NULL, 0, a->tk);
+    case E_VERIFY: return md5hip_batch_verify_iov(b, a->segs, a->first, a->n, a->dig, a->ok);
+    case E_POOL: return md5hip_pool_submit(p, a->ptrs, a->lens, a->n, a->dig);
+    case E_POOL_ASYNC: return md5hip_pool_submit_async(p, a->ptrs, a->lens, a->n, a->dig, a->tk);
+    case E_POOL_IOV: return md5hip_pool_submit_iov(p, a->segs, a->first, a->n, a->dig);
+    case E_POOL_IOV_ASYNC: return md5hip_pool_submit_iov_async(p, a->segs, a->first, a->n, a->dig, a->tk);
+    case E_POOL_FIXED: return md5hip_pool_host_fixed(p, a->base, a->n, a->len, a->stride, a->dig);
+    case E_POOL_VERIFY: return md5hip_pool_verify_iov(p, a->segs, a->first, a->n, a->dig, a->ok);
+    }
+    return 12345;
+}
+
+#define TK_SENTINEL 0x7777u
+static int g_arg_bad;
+
+/* one call: `want` returned, and *ticket (where the call has one) zeroed */
+static void arg_expect(int e, const struct arg_set *a, const char *what, int want)
+{
+    uint64_t tk = TK_SENTINEL;
+    struct arg_set c = *a;
+    if (c.tk) c.tk = &tk;
+    const int rc = arg_call(e, &c);
+    if (rc != want || (c.tk && tk != 0)) {
+        printf("FAIL arguments: %s, %s%s: rc %d (want %d), *ticket %llu (want 0)\n", g_entries[e].name, what,
+               c.tk || g_entries[e].ticket == TK_NONE ? "" : " (no ticket)", rc, want,
+               (unsigned long long)(c.tk ? tk : 0));
+        g_arg_bad++;
+    }
+}
+
+static int arguments(void)
+{
+    enum { N = 4 };
+    const int devs[2] = {0, 1};
+    md5hip_pool *pool;
+    int rc = md5hip_pool_create(devs, 2, 1u << 20, 2, &pool);
+    if (rc) { printf("FAIL arguments pool %d\n", rc); return 1; }
+    const void *ptrs[N], *ptrs_bad[N];
+    uint32_t lens[N];
+    uint64_t dptrs[N], dptrs_bad[N], tk_slot;
+    struct md5hip_iov segs[2 * N], segs_bad[2 * N];
+    const uint64_t first[N + 1] = {0, 2, 4, 6, 8}, first_off[N + 1] = {1, 2, 4, 6, 8},
+                   first_dec[N + 1] = {0, 2, 1, 6, 8};
+    unsigned char dig[N][16], ok[N];
+    memset(dig, 0, sizeof dig);
+    for (int i = 0; i < N; i++) {
+        ptrs[i] = ptrs_bad[i] = g_heap + 256 * i;
+        lens[i] = 100;
+        dptrs[i] = dptrs_bad[i] = (uint64_t)(uintptr_t)ptrs[i];
+        segs[2 * i] = (struct md5hip_iov){ptrs[i], 40};
+        segs[2 * i + 1] = (struct md5hip_iov){(const unsigned char *)ptrs[i] + 40, 60};
+    }
+    memcpy(segs_bad, segs, sizeof segs);
+    ptrs_bad[N - 1] = NULL;                            /* the last chunk: NULL, 100 bytes */
+    dptrs_bad[N - 1] = 0;
+    segs_bad[2 * N - 1].base = NULL;
+    for (int e = 0; e < E_COUNT; e++) {
+        const int shape = g_entries[e].shape, tkm = g_entries[e].ticket;
+        /* an optional ticket: every case with one and without */
+        for (int with = tkm != TK_NONE; with >= (tkm == TK_REQUIRED); with--) {
+            const struct arg_set good = {g_entries[e].pool ? (void *)pool : (void *)g_b, ptrs, lens, dptrs, segs,
+                                         first, g_heap, 100, 256, N, &dig[0][0], ok, with ? &tk_slot : NULL};
+            struct arg_set a = good;
+            a.h = NULL;
+            arg_expect(e, &a, "NULL handle", -EINVAL);
+            a = good, a.n = 0;
+            arg_expect(e, &a, "n == 0", 0);
+            a = good, a.dig = NULL;
+            arg_expect(e, &a, g_entries[e].verify ? "NULL expected" : "NULL digests", -EINVAL);
+            if (g_entries[e].verify) {
+                a = good, a.ok = NULL;
+                arg_expect(e, &a, "NULL ok", -EINVAL);
+            }
+            a = good;
+            if (shape == SH_PTRS) a.ptrs = NULL;
+            if (shape == SH_IOV) a.segs = NULL;
+            if (shape == SH_DEV) a.dptrs = NULL;
+            if (shape == SH_FIXED) a.base = NULL;
+            arg_expect(e, &a, "NULL source array", -EINVAL);
+            if (shape != SH_FIXED) {
+                a = good;
+                if (shape == SH_IOV) a.first = NULL;
+                else a.lens = NULL;
+                arg_expect(e, &a, shape == SH_IOV ? "NULL seg_first" : "NULL lens", -EINVAL);
+                a = good, a.ptrs = ptrs_bad, a.dptrs = dptrs_bad, a.segs = segs_bad;
+                arg_expect(e, &a, "NULL pointer with a length at the last index", -EINVAL);
+            }
+            if (shape == SH_IOV) {
+                a = good, a.first = first_off;
+                arg_expect(e, &a, "seg_first[0] != 0", -EINVAL);
+                a = good, a.first = first_dec;
+                arg_expect(e, &a, "decreasing seg_first", -EINVAL);
+            }
+            if (shape == SH_FIXED) {
+                a = good, a.len = 257;
+                arg_expect(e, &a, "len > stride", -EINVAL);
+            }
+        }
+        if (tkm == TK_REQUIRED) {
+            struct arg_set a = {g_entries[e].pool ? (void *)pool : (void *)g_b, ptrs, lens, dptrs, segs,
+                                first, g_heap, 100, 256, N, &dig[0][0], ok, NULL};
+            arg_expect(e, &a, "NULL ticket", -EINVAL);
+        }
+    }
+    struct md5hip_batcher_stats st;
+    md5hip_batcher_get_stats(g_b, &st);
+    if (st.submissions) {
+        printf("FAIL arguments: %llu calls reached the batcher\n", (unsigned long long)st.submissions);
+        g_arg_bad++;
+    }
+    md5hip_pool_destroy(pool);
+    if (!g_arg_bad) printf("arguments: %d entries refuse each wrong argument, *ticket zeroed\n", (int)E_COUNT);
+    return g_arg_bad != 0;
+}
+
 /* a hang is a failure, not a stuck test */
 static void *watchdog(void *arg)
 {
@@ -987,6 +1252,7 @@ int main(int argc, char **argv)
     pthread_t wd;
     pthread_create(&wd, NULL, watchdog, &wd_secs);
     pthread_detach(wd);
+    if (arguments()) return 1;
     if (blocked_callers(12)) return 1;
     if (large_device()) return 1;
     if (device_lost()) return 1;
@@ -1023,6 +1289,7 @@ int main(int argc, char **argv)
     }
     if (fragmented()) return 1;
     if (partly_pinned()) return 1;
+    if (pool_split_iov()) return 1;
     const int devs[3] = {0, 1, 2};
     if ((rc = md5hip_pool_create(devs, 3, 1u << 20, 2, &g_pool))) { printf("FAIL pool %d\n", rc); return 1; }
     enum { T = 10 };

@@ -169,26 +169,32 @@ static int fake_state(md5hip_batcher *b, uint64_t t, int advance, int *err)
     return done;
 }
 
-int md5hip_submit_as(md5hip_batcher *b, int kind, uint32_t fastcrc, const void *const *ptrs,
-                     const uint32_t *lens, const struct md5hip_iov *segs, const uint64_t *seg_first,
-                     uint64_t n, unsigned char *digests, uint64_t *ticket, int urgent)
+int md5hip_submit_src(md5hip_batcher *b, int kind, uint32_t fastcrc, const struct md5hip_src *src, uint64_t lo,
+                      uint64_t hi, unsigned char *digests, uint64_t *ticket, int urgent)
 {
     (void)fastcrc;
     (void)urgent;
     if (ticket) *ticket = 0;
+    const uint64_t n = hi - lo;
     if (n == 0) return 0;
     if (md5hip_batcher_health(b)) return -ENODEV;
     const uint32_t dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
     uint64_t weight = 0;
     for (uint64_t i = 0; i < n; i++) {
-        if (ptrs) {
-            const struct md5hip_iov one = {ptrs[i], lens[i]};
+        const uint64_t c = src->first + lo + i;         /* the chunk in the caller's arrays */
+        if (src->kind == MD5HIP_SRC_PTRS) {
+            const struct md5hip_iov one = {src->ptrs[c], src->lens[c]};
             digest_one(kind, &one, 1, digests + (size_t)dsz * i);
-            weight += (uint64_t)lens[i] + 64;
-        } else {
-            digest_one(kind, segs + seg_first[i], seg_first[i + 1] - seg_first[i], digests + (size_t)dsz * i);
-            for (uint64_t k = seg_first[i]; k < seg_first[i + 1]; k++) weight += segs[k].len;
+            weight += (uint64_t)src->lens[c] + 64;
+        } else if (src->kind == MD5HIP_SRC_IOV) {
+            const uint64_t *sf = src->seg_first;
+            digest_one(kind, src->segs + sf[c], sf[c + 1] - sf[c], digests + (size_t)dsz * i);
+            for (uint64_t k = sf[c]; k < sf[c + 1]; k++) weight += src->segs[k].len;
             weight += 64;
+        } else {
+            const struct md5hip_iov one = {src->base + c * src->stride, src->len};
+            digest_one(kind, &one, 1, digests + (size_t)dsz * i);
+            weight += (uint64_t)src->len + 64;
         }
     }
     uint64_t t;
@@ -196,30 +202,6 @@ int md5hip_submit_as(md5hip_batcher *b, int kind, uint32_t fastcrc, const void *
     fake_submit(b, kind, weight, &t, &failed);
     if (failed) memset(digests, 0xAA, (size_t)dsz * n);  /* what a failed launch leaves */
     if (!ticket) {                                      /* synchronous */
-        int err = 0;
-        while (!fake_state(b, t, 1, &err)) {}
-        return err;
-    }
-    *ticket = t;
-    return 0;
-}
-
-int md5hip_host_fixed_as(md5hip_batcher *b, int kind, uint32_t fastcrc, const void *h_base, uint64_t n,
-                         uint32_t len, uint64_t stride, unsigned char *digests, uint64_t *ticket)
-{
-    (void)fastcrc;
-    if (ticket) *ticket = 0;
-    if (md5hip_batcher_health(b)) return -ENODEV;
-    const uint32_t dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
-    for (uint64_t i = 0; i < n; i++) {
-        const struct md5hip_iov one = {(const unsigned char *)h_base + i * stride, len};
-        digest_one(kind, &one, 1, digests + (size_t)dsz * i);
-    }
-    uint64_t t;
-    int failed;
-    fake_submit(b, kind, n * ((uint64_t)len + 64), &t, &failed);
-    if (failed) memset(digests, 0xAA, (size_t)dsz * n);
-    if (!ticket) {
         int err = 0;
         while (!fake_state(b, t, 1, &err)) {}
         return err;

@@ -26,6 +26,9 @@ scattered in pieces; the fake planner rejects a histogram that misses a
 chunk.  Then host_fixed over a source pinned only in part (first half,
 two adjacent pinned blocks, an extent the runtime will not tell): staged,
 never DMA'd from past a page-locked range; wholly pinned: read in place.
+Before all of it, every public submit and verify entry is called with one
+argument wrong; after it, the pool splits page lists three ways with the later
+parts starting mid-list (staged and registered, MD5 and fastcrc).
 Runs under ASan+UBSan and under ThreadSanitizer
 (which found the unlocked gather-mode read in submit(), now atomic)."""
 import os
@@ -55,6 +58,8 @@ def _build_and_run(name, san, env_extra, secs):
     out = subprocess.run([exe, str(secs)], capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     assert out.stdout.strip().endswith("batcher ok")
+    assert "arguments: 17 entries refuse each wrong argument, *ticket zeroed" in out.stdout
+    assert "split page lists: 3 parts of more than 64 chunks read in place" in out.stdout
     assert "blocked callers: 12 rounds x 64 waiters on one slot ok" in out.stdout
     assert "large device submissions ok" in out.stdout
     assert "device lost: -EIO / -ENODEV / failover ok" in out.stdout
