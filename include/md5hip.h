@@ -30,7 +30,11 @@
 extern "C" {
 #endif
 
-/* ABI 5 (round 6): md5hip_order_stable_scratch / md5hip_order_device_stable
+/* ABI 5 + md5crc32: the one-pass MD5 + CRC-32 digest kind
+ * (MD5HIP_DIGEST_MD5_CRC32, struct md5hip_md5crc32), md5crc32hip_fixed /
+ * md5crc32hip_desc and md5hip_batch_upgrade_iov / md5hip_pool_upgrade_iov
+ * (appended; the version number is unchanged, a caller finds them by symbol).
+ * ABI 5 (round 6): md5hip_order_stable_scratch / md5hip_order_device_stable
  * (appended; the batcher's large slots use them); md5hip_batch_host_fixed
  * reads a source in place only if it is pinned over its whole range.
  * ABI 4 (round 5): device failure -- md5hip_batcher_health /
@@ -181,6 +185,27 @@ int crc32hip_desc_variant(const void *d_base, const uint64_t *d_offsets, const u
                           void *stream, int variant);
 
 /*
+ * MD5 and CRC-32 of the same bytes in one pass: a cache moving from CRC-32
+ * block headers to MD5 ones needs both values of a block at the same moment
+ * (verify the stored CRC, seal the MD5), and two launches would stage and
+ * read the bytes twice.  Record i (32 bytes, 16-B aligned array):
+ *   md5   MD5(chunk i), md5.c byte order                    bytes  0..15
+ *   crc   crc32(chunk i) (whole chunk; no fastcrc window)   bytes 16..19, LE
+ *   zero  always written as 0                               bytes 20..31
+ * Same conventions and argument rules as the MD5 entries.
+ */
+struct md5hip_md5crc32 {
+    unsigned char md5[16];
+    uint32_t crc;
+    uint32_t zero[3];
+};
+int md5crc32hip_fixed(const void *d_base, uint64_t n, uint32_t len, uint64_t stride,
+                      struct md5hip_md5crc32 *d_out, void *stream);
+int md5crc32hip_desc(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+                     const uint32_t *d_order, uint64_t n, struct md5hip_md5crc32 *d_out,
+                     void *stream);
+
+/*
  * Host helper: order[] = indices of lens[] sorted by MD5 block count,
  * descending (stable counting sort, O(n)).  Synchronous, host memory.
  */
@@ -285,8 +310,13 @@ typedef struct md5hip_batcher md5hip_batcher;
 
 /* What a batcher computes per chunk (default MD5, 16 bytes).  CRC32 gives
  * netcache's own 4-byte block checksum, with the fastcrc head^tail window
- * (0 = whole block), i.e. exactly what blk_make_crc returns. */
-enum md5hip_digest_kind { MD5HIP_DIGEST_MD5 = 0, MD5HIP_DIGEST_CRC32 = 1 };
+ * (0 = whole block), i.e. exactly what blk_make_crc returns.  MD5_CRC32 gives
+ * both from one read of the bytes as a 32-byte struct md5hip_md5crc32 per
+ * chunk (fastcrc must be 0); every submit entry then takes and returns
+ * 32-byte records where it says "digests".  A build of the batcher without
+ * the device library's md5crc32hip_* launchers refuses that kind with
+ * -ENOSYS (set_digest and the upgrade entries); libmd5hip.so always has them. */
+enum md5hip_digest_kind { MD5HIP_DIGEST_MD5 = 0, MD5HIP_DIGEST_CRC32 = 1, MD5HIP_DIGEST_MD5_CRC32 = 2 };
 
 int md5hip_batcher_create(int device, uint64_t slice_bytes, uint32_t nslots,
                           md5hip_batcher **out);
@@ -453,12 +483,23 @@ int md5_batch_flush(md5hip_batcher *b);
 
 /* Batched verify (cache read / write verify sites, blk_io.c:665-704,
  * bc_mgr.c:1464-1492): ok[i] = (digest of chunk i == expected[i]), expected
- * holding 16 (MD5) or 4 (CRC32) bytes per chunk.  Returns the number of
+ * holding 16 (MD5), 4 (CRC32) or 32 (MD5_CRC32: whole records, the zero
+ * bytes included) bytes per chunk.  Returns the number of
  * mismatches (>= 0) or -errno; the caller keeps its per-block EAGAIN /
  * inode-reset policy (blk_io.c:693-703). */
 int md5hip_batch_verify_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
                             const uint64_t *seg_first, uint64_t n, const void *expected,
                             unsigned char *ok);
+
+/* Verify the stored CRC-32 of every chunk and produce its MD5 in ONE pass
+ * (the MD5_CRC32 kind for this call only, whatever kind the batcher is set
+ * to): ok[i] = (crc32(chunk i) == want_crc[i]), md5_out + 16*i = MD5(chunk i)
+ * for every chunk, mismatching ones included.  Returns the number of
+ * mismatches (>= 0) or -errno; on -errno nothing is written to ok or
+ * md5_out. */
+int md5hip_batch_upgrade_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
+                             const uint64_t *seg_first, uint64_t n, const uint32_t *want_crc,
+                             unsigned char *ok, unsigned char *md5_out);
 
 /*
  * Zero-copy input.  md5hip_host_register pins and device-maps host memory
@@ -528,6 +569,10 @@ int md5hip_pool_verify_iov(md5hip_pool *p, const struct md5hip_iov *segs,
                            unsigned char *ok);
 int md5hip_pool_host_fixed(md5hip_pool *p, const void *h_base, uint64_t n, uint32_t len,
                            uint64_t stride, unsigned char *digests);
+/* md5hip_batch_upgrade_iov on the pool (routed and split as any submission). */
+int md5hip_pool_upgrade_iov(md5hip_pool *p, const struct md5hip_iov *segs,
+                            const uint64_t *seg_first, uint64_t n, const uint32_t *want_crc,
+                            unsigned char *ok, unsigned char *md5_out);
 /* Asynchronous forms, ticket semantics as md5_batch_submit_async: the call
  * returns once the chunks are staged, *ticket (0 for an empty submission)
  * completes when every device holding its chunks has delivered them, and

@@ -11,6 +11,7 @@
 //   Md5Hasher<kLat>  md5.c:153-265 (MD5Init / Update / Final per chunk)
 //   Crc32Hasher      netcache crc32.c:186-240 (slicing-by-8 over LDS tables)
 //   Crc32PermHasher  the same CRC, slicing-by-4 over 16 lane-private table copies
+//   Md5Crc32Hasher   both of the above over one read of the bytes (32-B records)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -321,6 +322,47 @@ struct Crc32PermHasher {
   }
   __device__ __forceinline__ void store(Out* out, uint64_t idx, const State& st) {
     out[idx] = st.c;
+  }
+};
+
+// ---------------------------------------------------------------------------
+// MD5 and CRC-32 of the same bytes in one pass (MD5HIP_DIGEST_MD5_CRC32): a
+// cache moving from CRC-32 headers to MD5 ones needs both values of a block
+// at once.  The two chains of a lane share every loaded word and nothing
+// else, so the CRC's LDS lookups issue under the MD5 steps.  Record i is 32
+// bytes: MD5 at 0..15 (md5.c:262-263), the CRC little-endian at 16..19, bytes
+// 20..31 zero; two 16-B stores, so every byte of a record is defined.
+// ---------------------------------------------------------------------------
+struct Md5Crc32State {
+  md5hip::State md5;
+  Crc32State crc;
+};
+
+struct alignas(16) Md5Crc32Record {
+  uint4 md5;
+  uint4 crc;      // x = the CRC-32, y z w = 0
+};
+
+struct Md5Crc32Hasher {
+  using State = Md5Crc32State;
+  using Out = Md5Crc32Record;
+  static constexpr int kLdsBytes = Crc32PermHasher::kLdsBytes;
+  Md5Hasher<false> m;
+  Crc32PermHasher c;
+  __device__ __forceinline__ void setup(uint8_t* l) { c.setup(l); }
+  __device__ __forceinline__ State init() { return State{m.init(), c.init()}; }
+  __device__ __forceinline__ void block(State& st, const uint4 (&w)[4]) {
+    m.block(st.md5, w);
+    c.block(st.crc, w);
+  }
+  __device__ __forceinline__ void finish(State& st, const uint8_t* tail, uint32_t r,
+                                         uint64_t len_bytes) {
+    m.finish(st.md5, tail, r, len_bytes);
+    c.finish(st.crc, tail, r, len_bytes);
+  }
+  __device__ __forceinline__ void store(Out* out, uint64_t idx, const State& st) {
+    out[idx].md5 = make_uint4(st.md5.a, st.md5.b, st.md5.c, st.md5.d);
+    out[idx].crc = make_uint4(st.crc.c, 0u, 0u, 0u);
   }
 };
 

@@ -102,14 +102,38 @@ static inline uint64_t md5hip_src_len(const struct md5hip_src *s, uint64_t i)
     return L;
 }
 
-/* digest bytes per chunk */
-static inline uint32_t md5hip_digest_size(int kind) { return kind == MD5HIP_DIGEST_CRC32 ? 4 : 16; }
+/* digest bytes per chunk (MD5_CRC32: one struct md5hip_md5crc32) */
+static inline uint32_t md5hip_digest_size(int kind)
+{
+    return kind == MD5HIP_DIGEST_CRC32 ? 4 : kind == MD5HIP_DIGEST_MD5_CRC32 ? 32 : 16;
+}
 
-/* a digest kind with its fastcrc window: MD5 takes none, CRC-32's is a
- * multiple of 4 (cfs_apix.c:2222-2236) */
+/* a digest kind with its fastcrc window: MD5 and MD5_CRC32 take none,
+ * CRC-32's is a multiple of 4 (cfs_apix.c:2222-2236) */
 static inline int md5hip_digest_valid(int kind, uint32_t fastcrc)
 {
-    return kind == MD5HIP_DIGEST_MD5 ? fastcrc == 0 : kind == MD5HIP_DIGEST_CRC32 && (fastcrc & 3u) == 0;
+    return kind == MD5HIP_DIGEST_MD5 || kind == MD5HIP_DIGEST_MD5_CRC32
+               ? fastcrc == 0
+               : kind == MD5HIP_DIGEST_CRC32 && (fastcrc & 3u) == 0;
+}
+
+/* The MD5_CRC32 launchers are weak references for the host objects: linked
+ * without the device library (the CPU tests' stand-in runtime has none) the
+ * batcher and the pool refuse the kind with -ENOSYS before anything is
+ * enqueued.  md5_kernels.hip defines them, so libmd5hip.so always has them. */
+#ifndef MD5HIP_DEFINES_MD5CRC32
+extern __typeof__(md5crc32hip_fixed) md5crc32hip_fixed __attribute__((weak));
+extern __typeof__(md5crc32hip_desc) md5crc32hip_desc __attribute__((weak));
+static inline int md5hip_md5crc32_present(void) { return &md5crc32hip_fixed && &md5crc32hip_desc; }
+#else
+static inline int md5hip_md5crc32_present(void) { return 1; }
+#endif
+/* 0, -EINVAL (no such kind / window) or -ENOSYS (MD5_CRC32 without its launchers) */
+static inline int md5hip_digest_usable(int kind, uint32_t fastcrc)
+{
+    if (!md5hip_digest_valid(kind, fastcrc)) return -EINVAL;
+    if (kind == MD5HIP_DIGEST_MD5_CRC32 && !md5hip_md5crc32_present()) return -ENOSYS;
+    return 0;
 }
 
 /* verify: ok[i] = digest i of `got` equals that of `expected`; the number of
@@ -121,6 +145,22 @@ static inline int md5hip_verify_count(const unsigned char *got, const void *expe
     int bad = 0;
     for (uint64_t i = 0; i < n; i++) {
         ok[i] = memcmp(got + (size_t)dsz * i, e + (size_t)dsz * i, dsz) == 0;
+        bad += !ok[i];
+    }
+    return bad;
+}
+
+/* upgrade: from n MD5_CRC32 records, ok[i] = (crc i == want_crc[i]) and
+ * md5_out + 16 i = md5 i (every chunk); the number of mismatches */
+static inline int md5hip_upgrade_count(const unsigned char *rec, const uint32_t *want_crc, uint64_t n,
+                                       unsigned char *ok, unsigned char *md5_out)
+{
+    int bad = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const unsigned char *r = rec + 32 * (size_t)i;
+        const uint32_t crc = (uint32_t)r[16] | (uint32_t)r[17] << 8 | (uint32_t)r[18] << 16 | (uint32_t)r[19] << 24;
+        memcpy(md5_out + 16 * (size_t)i, r, 16);
+        ok[i] = crc == want_crc[i];
         bad += !ok[i];
     }
     return bad;

@@ -1194,6 +1194,56 @@ crc32_desc_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__
     desc_xpose_group<2>(h, base, DescArrays{offs, lens, order}, n, gi * 64u, out, img);
 }
 
+// MD5 + CRC-32 in one pass (Md5Crc32Hasher, 32-B records) in XDMA16's frame:
+// the 64 KiB tables beside twelve 8 KiB images, one 768-thread workgroup per
+// CU, 3 waves per SIMD.  A throughput kind: no small-batch variants.
+__global__ void __launch_bounds__(768)
+md5crc32_fixed_xdma16(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uint64_t stride,
+                      Md5Crc32Record* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[Md5Crc32Hasher::kLdsBytes + 12 * 8192];
+  Md5Crc32Hasher h;
+  h.setup(lds);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint8_t* img = lds + Md5Crc32Hasher::kLdsBytes + wave * 8192u;
+  const uint64_t ngroups = (n + 63) / 64;
+  for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u)
+    xdma_group(h, base, n, len, stride, gi * 64u, out, img);
+}
+
+// Fixed-length chunks as a descriptor source: chunk i at i * stride, flen
+// bytes (a base or stride off the 16-B grid, or a stride past xdma_group's
+// 32-bit offsets).
+struct FixedChunks {
+  uint64_t stride;
+  uint32_t flen;
+  static constexpr bool kPairXor = false;
+  static constexpr bool kAbs = false;
+  __device__ __forceinline__ uint64_t index(uint64_t i) const { return i; }
+  __device__ __forceinline__ uint64_t off(uint64_t c) const { return c * stride; }
+  __device__ __forceinline__ uint32_t len(uint64_t) const { return flen; }
+};
+
+// kImplicit: FixedChunks (offs, lens and order unused), else DescArrays.
+template <bool kImplicit>
+__global__ void __launch_bounds__(768)
+md5crc32_desc_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
+                     const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order,
+                     uint64_t n, uint64_t stride, uint32_t flen, Md5Crc32Record* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[Md5Crc32Hasher::kLdsBytes + 12 * 8192];
+  Md5Crc32Hasher h;
+  h.setup(lds);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint8_t* img = lds + Md5Crc32Hasher::kLdsBytes + wave * 8192u;
+  const uint64_t ngroups = (n + 63) / 64;
+  for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u) {
+    if constexpr (kImplicit)
+      desc_xpose_group<2, Md5Crc32Hasher, 0, FixedChunks>(h, base, FixedChunks{stride, flen}, n, gi * 64u,
+                                                         out, img);
+    else
+      desc_xpose_group<2>(h, base, DescArrays{offs, lens, order}, n, gi * 64u, out, img);
+  }
+}
+
 // fastcrc (blk_io.c:408-424) through the same LDS-DMA loader: each 64-row
 // wave group is 32 chunks' head and tail windows (FastWindows), F bytes each,
 // so a wave-instruction still reads whole 128-B runs of 8 windows; lane pairs

@@ -33,6 +33,7 @@ template __global__ void crc32_desc<true>(const uint8_t*, const uint64_t*, const
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "../../include/md5hip.h"
+#define MD5HIP_DEFINES_MD5CRC32   // the launchers are defined here (md5_internal.h)
 #include "md5_internal.h"
 
 using namespace md5hip;
@@ -401,6 +402,49 @@ int crc32hip_desc_variant(const void* d_base, const uint64_t* d_offsets, const u
   // XDMA16: one 768-thread workgroup per CU, LDS-DMA images
   hipLaunchKernelGGL(crc32_desc_xdma16, dim3(per_cu_grid(n)), dim3(768), 0, s,
                      (const uint8_t*)d_base, d_offsets, d_lens, d_order, n, d_crcs);
+  return launched();
+}
+
+// MD5 + CRC-32 in one pass (32-B records, md5hip.h).  One frame for every
+// batch: XDMA16's 768-thread workgroup per CU.  Chunk starts off the 16-B
+// grid, or a stride past the fixed loader's 32-bit offsets, take the
+// descriptor kernel with implicit offsets (its lane-direct branch covers the
+// unaligned waves).
+int md5crc32hip_fixed(const void* d_base, uint64_t n, uint32_t len, uint64_t stride,
+                      struct md5hip_md5crc32* d_out, void* stream) {
+  static_assert(sizeof(md5hip_md5crc32) == sizeof(Md5Crc32Record) && sizeof(Md5Crc32Record) == 32,
+                "record layout");
+  if (n == 0) return 0;
+  if (!d_base || !d_out || len > stride) return -EINVAL;
+  if (((uintptr_t)d_out & 15u) != 0) return -EINVAL;
+  if (int e = device_ok()) return e;
+  if ((n + 63) / 64 > 0x7fffffffull) return -EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const uint8_t* base = (const uint8_t*)d_base;
+  Md5Crc32Record* out = reinterpret_cast<Md5Crc32Record*>(d_out);
+  const bool aligned = ((uintptr_t)base & 15u) == 0 && (stride & 15u) == 0;
+  if (aligned && stride < (1ull << 31) / 64) {
+    hipLaunchKernelGGL(md5crc32_fixed_xdma16, dim3(per_cu_grid(n)), dim3(768), 0, s, base, n, len,
+                       stride, out);
+    return launched();
+  }
+  hipLaunchKernelGGL(md5crc32_desc_xdma16<true>, dim3(per_cu_grid(n)), dim3(768), 0, s, base,
+                     (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, n,
+                     stride, len, out);
+  return launched();
+}
+
+int md5crc32hip_desc(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
+                     const uint32_t* d_order, uint64_t n, struct md5hip_md5crc32* d_out,
+                     void* stream) {
+  if (n == 0) return 0;
+  if (!d_base || !d_offsets || !d_lens || !d_out) return -EINVAL;
+  if (((uintptr_t)d_out & 15u) != 0) return -EINVAL;
+  if (int e = device_ok()) return e;
+  if ((n + 63) / 64 > 0x7fffffffull) return -EINVAL;
+  hipLaunchKernelGGL(md5crc32_desc_xdma16<false>, dim3(per_cu_grid(n)), dim3(768), 0,
+                     (hipStream_t)stream, (const uint8_t*)d_base, d_offsets, d_lens, d_order, n,
+                     (uint64_t)0, 0u, reinterpret_cast<Md5Crc32Record*>(d_out));
   return launched();
 }
 

@@ -141,7 +141,9 @@ int md5hip_pool_ndev(const md5hip_pool *p) { return p ? (int)p->ndev : -EINVAL; 
 
 int md5hip_pool_set_digest(md5hip_pool *p, int kind, uint32_t fastcrc)
 {
-    if (!p || !md5hip_digest_valid(kind, fastcrc)) return -EINVAL;
+    if (!p) return -EINVAL;
+    const int u = md5hip_digest_usable(kind, fastcrc);
+    if (u) return u;
     pthread_mutex_lock(&p->mu);
     p->kind = kind;
     p->fastcrc = fastcrc;
@@ -670,5 +672,26 @@ int md5hip_pool_verify_iov(md5hip_pool *p, const struct md5hip_iov *segs, const 
     rc = pool_submit(p, &s, n, got, NULL, kind, fastcrc);
     if (rc == 0) rc = md5hip_verify_count(got, expected, dsz, n, ok);
     free(got);
+    return rc;
+}
+
+/* md5hip_batch_upgrade_iov on the pool: one MD5_CRC32 submission of this
+ * call's own, routed and split as any other. */
+int md5hip_pool_upgrade_iov(md5hip_pool *p, const struct md5hip_iov *segs, const uint64_t *seg_first,
+                            uint64_t n, const uint32_t *want_crc, unsigned char *ok,
+                            unsigned char *md5_out)
+{
+    if (!p) return -EINVAL;
+    int rc = md5hip_digest_usable(MD5HIP_DIGEST_MD5_CRC32, 0);
+    if (rc) return rc;
+    if (n == 0) return 0;
+    if (!want_crc || !ok || !md5_out) return -EINVAL;
+    const struct md5hip_src s = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+    if ((rc = md5hip_src_check(&s, n))) return rc;
+    unsigned char *rec = malloc(32 * (size_t)n);
+    if (!rec) return -ENOMEM;
+    rc = pool_submit(p, &s, n, rec, NULL, MD5HIP_DIGEST_MD5_CRC32, 0);
+    if (rc == 0) rc = md5hip_upgrade_count(rec, want_crc, n, ok, md5_out);
+    free(rec);
     return rc;
 }

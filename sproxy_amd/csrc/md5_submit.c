@@ -200,7 +200,7 @@ struct slot {
     const uint32_t *dh_len;
     int desc_direct;                  /* the planned launch reads dh_off / dh_len in place */
     uint32_t *h_ord, *d_ord;
-    unsigned char *h_dig, *d_dig;     /* 16 * maxn */
+    unsigned char *h_dig, *d_dig;     /* 32 * maxn (the largest digest, MD5_CRC32's record) */
     int direct;                       /* the kernel wrote the one device segment in place */
     struct md5hip_seg *h_seg, *d_seg; /* zero-copy gather table, `segcap` entries */
     void **b_dst, **b_src;            /* DMA-batch gather arrays (plain host memory) */
@@ -270,7 +270,7 @@ enum watch_policy { WATCH_POLICY_SPIN = 0, WATCH_POLICY_TAIL = 1, WATCH_POLICY_B
 
 struct md5hip_batcher {
     int device;
-    int kind;          /* MD5HIP_DIGEST_MD5 or MD5HIP_DIGEST_CRC32 */
+    int kind;          /* enum md5hip_digest_kind */
     uint32_t fastcrc;  /* CRC-32 head^tail window (blk_io.c:408-424), 0 = whole block */
     uint32_t nslots;
     uint64_t cap;      /* staging bytes per slot */
@@ -457,6 +457,8 @@ static int slot_enqueue(md5hip_batcher *b, struct slot *sl)
         if (sl->chain_ev && hipStreamWaitEvent(sl->stream, sl->chain_ev, 0) != hipSuccess) return -EIO;
         rc = sl->kind == MD5HIP_DIGEST_CRC32
                  ? crc32hip_fixed(src, n, sl->fx_len, sl->fx_stride, sl->fastcrc, (uint32_t *)dst, sl->stream)
+             : sl->kind == MD5HIP_DIGEST_MD5_CRC32
+                 ? md5crc32hip_fixed(src, n, sl->fx_len, sl->fx_stride, (struct md5hip_md5crc32 *)dst, sl->stream)
                  : md5hip_digest_fixed(src, n, sl->fx_len, sl->fx_stride, dst, sl->stream);
         if (rc) return rc;
         if (hipEventRecord(sl->kdone, sl->stream)) return -EIO;
@@ -499,6 +501,8 @@ static int slot_enqueue(md5hip_batcher *b, struct slot *sl)
                                          md5hip_crc_desc_choice(sl->fastcrc ? 2 * n : n,
                                                                 sl->fastcrc ? sl->fastcrc
                                                                             : sl->load / n - 64))
+             : sl->kind == MD5HIP_DIGEST_MD5_CRC32      /* one frame for every batch: the plan's order only */
+                 ? md5crc32hip_desc(sl->d_data, doff, dlen, ord, n, (struct md5hip_md5crc32 *)dst, sl->stream)
                  : md5hip_digest_desc_variant(sl->d_data, doff, dlen, ord, n,
                                               dst, sl->stream, dvar);
         if (rc) return rc;
@@ -1116,12 +1120,12 @@ static int batcher_new(int device, uint64_t slice_bytes, uint32_t nslots, uint64
         CK(hipHostGetDevicePointer((void **)&sl->dh_off, sl->h_off, 0));
         CK(hipHostGetDevicePointer((void **)&sl->dh_len, sl->h_len, 0));
         CK(hipHostMalloc((void **)&sl->h_ord, 4 * b->maxn, hipHostMallocDefault));
-        CK(hipHostMalloc((void **)&sl->h_dig, 16 * b->maxn, hipHostMallocDefault));
+        CK(hipHostMalloc((void **)&sl->h_dig, 32 * b->maxn, hipHostMallocDefault));
         CK(hipMalloc((void **)&sl->d_data, b->cap));
         CK(hipMalloc((void **)&sl->d_off, 8 * b->maxn));
         CK(hipMalloc((void **)&sl->d_len, 4 * b->maxn));
         CK(hipMalloc((void **)&sl->d_ord, 4 * b->maxn));
-        CK(hipMalloc((void **)&sl->d_dig, 16 * b->maxn));
+        CK(hipMalloc((void **)&sl->d_dig, 32 * b->maxn));
         CK(hipHostMalloc((void **)&sl->h_seg, sizeof(struct md5hip_seg) * b->segcap, hipHostMallocDefault));
         CK(hipMalloc((void **)&sl->d_seg, sizeof(struct md5hip_seg) * b->segcap));
         CK(hipHostMalloc((void **)&sl->h_dsc, sizeof(struct md5hip_seg) * b->segcap, hipHostMallocDefault));
@@ -1193,7 +1197,9 @@ static void drain(md5hip_batcher *b)
 
 int md5hip_batcher_set_digest(md5hip_batcher *b, int kind, uint32_t fastcrc)
 {
-    if (!b || !md5hip_digest_valid(kind, fastcrc)) return -EINVAL;
+    if (!b) return -EINVAL;
+    const int u = md5hip_digest_usable(kind, fastcrc);
+    if (u) return u;
     struct dev_guard g;
     if (dev_enter(&g, b->device)) return -ENODEV;  /* drain may launch the open slot */
     pthread_mutex_lock(&b->mu);
@@ -2144,9 +2150,10 @@ int md5hip_verify_iov_as(md5hip_batcher *b, int kind, uint32_t fastcrc,
     if (!b) return -EINVAL;
     if (n == 0) return 0;
     if (!expected || !ok) return -EINVAL;
-    if (!md5hip_digest_valid(kind, fastcrc)) return -EINVAL;
+    int rc;
+    if ((rc = md5hip_digest_usable(kind, fastcrc))) return rc;
     const struct md5hip_src src = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
-    int rc = md5hip_src_check(&src, n);
+    rc = md5hip_src_check(&src, n);
     if (rc) return rc;
     const uint32_t dsz = md5hip_digest_size(kind);
     unsigned char *got = malloc((size_t)dsz * n);
@@ -2166,4 +2173,26 @@ int md5hip_batch_verify_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
     uint32_t fastcrc;
     md5hip_batcher_get_digest(b, &kind, &fastcrc);
     return md5hip_verify_iov_as(b, kind, fastcrc, segs, seg_first, n, expected, ok);
+}
+
+/* Verify the stored CRC-32 and produce the MD5 of every chunk in one pass:
+ * an MD5_CRC32 submission of this call's own (md5hip_verify_iov_as's
+ * mechanism: the batcher's kind is not touched). */
+int md5hip_batch_upgrade_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
+                             const uint64_t *seg_first, uint64_t n, const uint32_t *want_crc,
+                             unsigned char *ok, unsigned char *md5_out)
+{
+    if (!b) return -EINVAL;
+    int rc = md5hip_digest_usable(MD5HIP_DIGEST_MD5_CRC32, 0);
+    if (rc) return rc;
+    if (n == 0) return 0;
+    if (!want_crc || !ok || !md5_out) return -EINVAL;
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+    if ((rc = md5hip_src_check(&src, n))) return rc;
+    unsigned char *rec = malloc(32 * (size_t)n);
+    if (!rec) return -ENOMEM;
+    rc = submit(b, &src, n, rec, 0, 0, NULL, MD5HIP_DIGEST_MD5_CRC32, 0, NULL);
+    if (rc == 0) rc = md5hip_upgrade_count(rec, want_crc, n, ok, md5_out);
+    free(rec);
+    return rc;
 }

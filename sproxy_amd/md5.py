@@ -237,6 +237,60 @@ def crc32_desc(base, offsets, lens, order=None, fastcrc: int = 0, out=None, stre
     return out
 
 
+def md5crc32_fixed(data, n: int = None, length: int = None, stride: int = None, out=None, stream=None):
+    """record[i] = MD5 and CRC-32 of chunk i from one read of its bytes
+    (struct md5hip_md5crc32): uint8 [n, 32] on device -- md5 at 0..15, the
+    CRC little-endian at 16..19, zeros at 20..31 (split_records)."""
+    _need_cuda(data, "data")
+    if n is None or length is None:
+        if data.dim() != 2:
+            raise ValueError("pass n and length, or a 2-D [n, length] tensor")
+        n, length = data.shape
+    stride = length if stride is None else stride
+    if n and (n - 1) * stride + length > data.numel() * data.element_size():
+        raise ValueError("batch extends past the end of `data`")
+    if out is None:
+        out = torch.empty((n, 32), dtype=torch.uint8, device=data.device)
+    _need_cuda(out, "out")
+    check("md5crc32hip_fixed",
+          lib().md5crc32hip_fixed(data.data_ptr(), n, length, stride, out.data_ptr(), _stream(stream)))
+    return out
+
+
+def md5crc32_desc(base, offsets, lens, order=None, out=None, stream=None):
+    """record[i] = MD5 and CRC-32 of base_bytes[offsets[i] : offsets[i] + lens[i]]
+    (as md5crc32_fixed): uint8 [n, 32] on device."""
+    _need_cuda(base, "base")
+    _need_cuda(offsets, "offsets")
+    _need_cuda(lens, "lens")
+    if offsets.dtype != torch.int64 or lens.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("offsets must be int64 and lens int32")
+    n = offsets.numel()
+    if lens.numel() != n:
+        raise ValueError("offsets and lens differ in length")
+    if order is not None:
+        _need_cuda(order, "order")
+        if order.numel() != n or order.dtype not in (torch.int32, torch.uint32):
+            raise ValueError("order must be an int32 permutation of range(n)")
+    if out is None:
+        out = torch.empty((n, 32), dtype=torch.uint8, device=base.device)
+    _need_cuda(out, "out")
+    check("md5crc32hip_desc",
+          lib().md5crc32hip_desc(base.data_ptr(), offsets.data_ptr(), lens.data_ptr(),
+                                 order.data_ptr() if order is not None else None, n, out.data_ptr(),
+                                 _stream(stream)))
+    return out
+
+
+def split_records(rec):
+    """(md5 uint8 [n, 16], crc uint32 [n]) of n 32-byte MD5_CRC32 records (a
+    host array, or a device tensor, which is copied to the host)."""
+    if torch is not None and isinstance(rec, torch.Tensor):
+        rec = rec.cpu().numpy()
+    r = np.ascontiguousarray(rec).view(np.uint8).reshape(-1, 32)
+    return r[:, :16].copy(), r[:, 16:20].copy().view("<u4").reshape(-1)
+
+
 class _Arena:
     """Owner of one md5hip_arena_alloc block, exposed through
     __cuda_array_interface__ so torch can wrap it without a copy."""
@@ -345,12 +399,14 @@ class Batcher:
     """The batcher (include/md5hip.h md5hip_batcher_*): a thread-safe,
     coalescing submission queue; tickets complete out of order."""
 
-    MD5, CRC32 = 0, 1
+    MD5, CRC32, MD5_CRC32 = 0, 1, 2
+    _dsz = {0: 16, 1: 4, 2: 32}
     GATHER_HOST, GATHER_DEVICE, GATHER_DMA, GATHER_AUTO = 0, 1, 2, 3
     _fn = dict(set_digest="md5hip_batcher_set_digest", set_gather="md5hip_batcher_set_gather",
                destroy="md5hip_batcher_destroy",
                submit="md5_batch_submit", submit_iov="md5_batch_submit_iov",
-               verify_iov="md5hip_batch_verify_iov", host_fixed="md5hip_batch_host_fixed",
+               verify_iov="md5hip_batch_verify_iov", upgrade_iov="md5hip_batch_upgrade_iov",
+               host_fixed="md5hip_batch_host_fixed",
                submit_async="md5_batch_submit_async", submit_iov_async="md5_batch_submit_iov_async",
                wait="md5_batch_wait", poll="md5_batch_poll", flush="md5_batch_flush",
                submit_device_async="md5_batch_submit_device_async",
@@ -376,9 +432,10 @@ class Batcher:
         return name, getattr(lib(), name)(self._h, *args)
 
     def set_digest(self, kind: int, fastcrc: int = 0):
-        """MD5 (16 B per chunk) or netcache CRC-32 (4 B, optional fastcrc window)."""
+        """MD5 (16 B per chunk), netcache CRC-32 (4 B, optional fastcrc window)
+        or MD5_CRC32 (both in one pass: 32-B records, see split_records)."""
         check(*self._call("set_digest", kind, fastcrc))
-        self.kind, self.dsz = kind, (16 if kind == self.MD5 else 4)
+        self.kind, self.dsz = kind, self._dsz[kind]
 
     def set_gather(self, mode: int):
         """HOST (memcpy into pinned staging), DEVICE (gather kernel over PCIe)
@@ -389,9 +446,9 @@ class Batcher:
     def _out(self, n):
         return np.empty((max(n, 1), self.dsz), dtype=np.uint8)
 
-    def _ret(self, out, n):
+    def _ret(self, out, n, dsz=None):
         out = out[:n]
-        return out if self.dsz == 16 else out.view("<u4").reshape(n)
+        return out.view("<u4").reshape(n) if (dsz or self.dsz) == 4 else out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -455,6 +512,7 @@ class Batcher:
         def __init__(self, batcher, ticket, out, n, keep, on_device=False):
             self.batcher, self.ticket, self._out, self.n, self._keep = batcher, ticket, out, n, keep
             self.on_device = on_device
+            self._dsz = batcher.dsz        # the kind at submission (a pool's may change before wait)
 
         def poll(self) -> bool:
             name, rc = self.batcher._call("poll", ctypes.c_uint64(self.ticket))
@@ -465,7 +523,7 @@ class Batcher:
         def wait(self):
             check(*self.batcher._call("wait", ctypes.c_uint64(self.ticket)))
             self._keep = None
-            return self._out if self.on_device else self.batcher._ret(self._out, self.n)
+            return self._out if self.on_device else self.batcher._ret(self._out, self.n, self._dsz)
 
     def submit_async(self, buffers) -> "Batcher.Pending":
         """md5_batch_submit_async: returns once the chunks are staged; the
@@ -634,6 +692,24 @@ class Batcher:
         del keep
         return ok[:n].astype(bool), rc
 
+    def upgrade_iov(self, chunks, want_crc):
+        """(ok[i] bool array, md5 uint8 [n, 16]): one MD5_CRC32 pass whatever
+        kind is set -- ok[i] = crc32(chunks[i]) == want_crc[i], and the MD5 of
+        every chunk (the mismatching ones too)."""
+        arr, fa, keep = self._iov(chunks)
+        n = len(chunks)
+        want = np.ascontiguousarray(want_crc, dtype=np.uint32)
+        if want.size != n:
+            raise ValueError("want_crc must hold one CRC-32 per chunk")
+        ok = np.empty(max(n, 1), dtype=np.uint8)
+        md5s = np.empty((max(n, 1), 16), dtype=np.uint8)
+        name, rc = self._call("upgrade_iov", arr, fa.ctypes.data, n, want.ctypes.data, ok.ctypes.data,
+                              md5s.ctypes.data)
+        if rc < 0:
+            check(name, rc)
+        del keep
+        return ok[:n].astype(bool), md5s[:n]
+
     def host_fixed(self, arr: np.ndarray, n: int, length: int, stride: int = None) -> np.ndarray:
         stride = length if stride is None else stride
         a = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
@@ -672,7 +748,8 @@ class Pool(Batcher):
     _fn = dict(set_digest="md5hip_pool_set_digest", set_gather="md5hip_pool_set_gather",
                destroy="md5hip_pool_destroy",
                submit="md5hip_pool_submit", submit_iov="md5hip_pool_submit_iov",
-               verify_iov="md5hip_pool_verify_iov", host_fixed="md5hip_pool_host_fixed",
+               verify_iov="md5hip_pool_verify_iov", upgrade_iov="md5hip_pool_upgrade_iov",
+               host_fixed="md5hip_pool_host_fixed",
                submit_async="md5hip_pool_submit_async", submit_iov_async="md5hip_pool_submit_iov_async",
                wait="md5hip_pool_wait", poll="md5hip_pool_poll", set_split="md5hip_pool_set_split")
 
@@ -747,7 +824,8 @@ def pool_plan(lens, nparts: int) -> np.ndarray:
 
 __all__ = ["init_ctx", "update_ctx", "final_ctx", "MD5Context", "MD5Init", "MD5Update", "MD5Final", "MD5_DIGEST_SIZE", "MD5HipError", "arena_empty",
            "plan_desc", "plan_desc_at",
-           "md5", "digest_fixed", "digest_desc", "crc32_fixed", "crc32_desc", "plan_order", "fill_synthetic", "Batcher",
+           "md5", "digest_fixed", "digest_desc", "crc32_fixed", "crc32_desc", "md5crc32_fixed", "md5crc32_desc",
+           "split_records", "plan_order", "fill_synthetic", "Batcher",
            "Pool", "Queue", "pool_plan", "CRC_VARIANTS", "DESC_VARIANTS",
            "register_host", "unregister_host",
            "variant_name", "resolve_variant", "VARIANTS", "crc_variant_name"]
