@@ -27,14 +27,32 @@ __attribute__((visibility("hidden")))
 int md5hip_gather_launch(const struct md5hip_seg *d_segs, uint64_t nseg, unsigned char *d_dst,
                          void *stream);
 
+/* Thresholds in 64-B blocks that the kernels (md5_kernels.h) and the planner
+ * (md5_plan.cc) share: a fed pair needs a chunk of two whole blocks; a
+ * HYBRID wave goes lane-direct from a longest chunk of 256 KiB. */
+enum { MD5HIP_FED_MIN_BLOCKS = 2, MD5HIP_HYBRID_LONG_BLOCKS = 4096 };
+
+/* Compute units of the current device, cached; 256 when it cannot be asked
+ * (md5_kernels.hip).  The planner's only way to the device. */
+__attribute__((visibility("hidden")))
+int md5hip_cu_count(void);
+
+/* The planner's entries for the launchers (md5_plan.cc): whether a batch of
+ * `ngroups` 64-chunk groups is small enough for fed pairs, and whether a
+ * full-CRC batch of n chunks of `len` bytes (0 = not known) runs split. */
+__attribute__((visibility("hidden")))
+int md5hip_fed_fits(uint64_t ngroups);
+__attribute__((visibility("hidden")))
+int md5hip_crc_split_fits(uint64_t n, uint64_t len);
+
 /* CRC kernel variant (enum crc32hip_variant) for a full-CRC descriptor batch
- * of n chunks whose mean length is known (md5_kernels.hip). */
+ * of n chunks whose mean length is known (md5_plan.cc). */
 __attribute__((visibility("hidden")))
 int md5hip_crc_desc_choice(uint64_t n, uint64_t mean_len);
 
 /* MD5 descriptor variant for a planned batch of `bytes` payload of which
  * `unlined_bytes` lie in chunks starting 16-B but not 128-B aligned: XDMA
- * becomes LINES past half (md5_kernels.hip). */
+ * becomes LINES past half (md5_plan.cc). */
 __attribute__((visibility("hidden")))
 int md5hip_lines_choice(int variant, uint64_t unlined_bytes, uint64_t bytes);
 

@@ -25,6 +25,7 @@
 
 #include "hashers.h"
 #include "md5_core.h"
+#include "md5_internal.h"   // thresholds shared with the planner
 
 namespace md5hip {
 
@@ -353,7 +354,7 @@ __device__ __forceinline__ bool long_outlier(const uint32_t* __restrict__ lens,
 
 // HYBRID's lane-direct threshold: a wave whose longest chunk has this many
 // 64-B blocks (256 KiB)
-constexpr uint32_t kHybridLongBlocks = 4096;
+constexpr uint32_t kHybridLongBlocks = MD5HIP_HYBRID_LONG_BLOCKS;
 
 // Where chunk i of a descriptor batch lies: (offset, length) arrays, packed
 // onto lanes in `order` when given.
@@ -1026,7 +1027,7 @@ __device__ __forceinline__ State fed_long_group(const uint8_t* __restrict__ base
 // body on wave 0 instead.
 // kImplicit: chunk i at base + i * stride, `flen` bytes (the fixed-length
 // API's small batches).
-constexpr uint32_t kFedMinBlocks = 2;
+constexpr uint32_t kFedMinBlocks = MD5HIP_FED_MIN_BLOCKS;
 
 template <bool kImplicit>
 __global__ void __launch_bounds__(128)
