@@ -152,9 +152,12 @@ def test_gpu_crc_full_size(cuda):
 @pytest.mark.gpu
 def test_gpu_crc_desc_netcache_blocks(cuda):
     """crc32hip_desc on the netcache shape (full blocks + ragged last blocks,
-    a wave without any 128-B stage, one unaligned chunk, > one grid of
-    64-chunk groups), ordered longest-first and unordered: the descriptor
-    kernel (crc32_desc_xdma16) and its lane-direct fallback against crc32.c."""
+    a wave without any 128-B stage, one unaligned chunk), ordered
+    longest-first and unordered: the descriptor kernel (crc32_desc_xdma16)
+    and its lane-direct fallback against crc32.c.  40,000 chunks are 625
+    groups: with one 12-wave workgroup per CU every wave hashes at most one
+    group on a part of 53 CUs or more, so the grid-stride loop's later trips
+    are tests/test_grid_trips.py's."""
     import torch
     rng = np.random.default_rng(777)
     for S, n in ((4096, 40000), (65536, 700)):
@@ -182,10 +185,13 @@ def test_gpu_fastcrc_xdma_windows(cuda, fast):
     """fastcrc through the LDS-DMA loader (crc32_fast_xdma16) and, for 64 and
     128, the pipelined lane-load kernel (crc32_fast_pipe, whose ragged and
     unaligned groups fall back to lane_range): head and tail windows as row
-    pairs, more 32-chunk groups than one grid holds, fixed
+    pairs, fixed
     16 KiB blocks and 16-B packed ragged blocks (windows of every alignment,
     blocks shorter than the window, empty blocks), against crc32.c's
-    blk_make_crc combination (blk_io.c:408-424) in the oracle."""
+    blk_make_crc combination (blk_io.c:408-424) in the oracle.  40,000 chunks
+    are 1,250 32-chunk groups: a wave of the persistent kernels (12 or 16 per
+    CU) hashes at most one on a part of 105 CUs or more, so the next group in
+    flight and the later trips are tests/test_grid_trips.py's."""
     import torch
     n, L = 40000, 16384
     d = torch.empty(n * L, dtype=torch.uint8, device=cuda)
