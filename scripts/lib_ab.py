@@ -8,7 +8,11 @@ Workloads:
   c2        md5hip_digest_fixed_variant xdma1nt on 1,048,576 x 16 KiB (bench C2)
   ctx       md5hip_update_ctx on 1,048,576 contexts x 16 KiB (bench --config ctx)
   ragged16  md5hip_digest_desc_variant XDMA, netcache blocks packed at 16 B
-  c3k3      BALANCED on 3 coalesced C3 batches (bench --config c3 coalesced leg)
+  ragged16_lines  the same batch under LINES
+  crc_fixed, crc_fast128, crc_fast4096, md5crc32_fixed, small_fed  (fixed_more_ab)
+  c3k3_balanced, c3k6_balanced  BALANCED on 3 / 6 coalesced C3 batches (bench --config c3 coalesced leg)
+  c3_hybrid  HYBRID on one C3 batch
+An A/A control is a second copy of the old build: --extra old2=build/ab/libmd5hip_old2.so.
 Prints one JSON object (ms per launch, hipEvent, interleaved rounds).
 usage: lib_ab.py [--rounds R] [--extra name=path ...]"""
 import argparse
@@ -34,6 +38,8 @@ def load(path):
     L.md5hip_init_ctx.argtypes = [vp, u64, vp]
     L.md5hip_digest_desc_variant.argtypes = [vp, vp, vp, vp, u64, vp, vp, ci]
     L.md5hip_digest_fixed_variant.argtypes = [vp, u64, ctypes.c_uint32, u64, vp, vp, ci]
+    L.crc32hip_fixed_variant.argtypes = [vp, u64, ctypes.c_uint32, u64, ctypes.c_uint32, vp, vp, ci]
+    L.md5crc32hip_fixed.argtypes = [vp, u64, ctypes.c_uint32, u64, vp, vp]
     return L
 
 
@@ -75,10 +81,13 @@ def ab(libs, run, out, rounds):
             run(L)
     torch.cuda.synchronize()
     ms = {k: [] for k in libs}
-    for _ in range(rounds):
-        for k, L in libs.items():
-            ms[k].append(round(timed(lambda: run(L)), 4))
-    return {"ms": ms, "equal": eq, "best_new_vs_old": round(min(ms["old"]) / min(ms["new"]), 4),
+    names = list(libs)
+    for r in range(rounds):              # each round starts one build further on: no build
+        for j in range(len(names)):      # always runs in the same place of the round
+            k = names[(r + j) % len(names)]
+            ms[k].append(round(timed(lambda: run(libs[k])), 4))
+    return {"ms": ms, "equal": eq, "median_ms": {k: sorted(v)[rounds // 2] for k, v in ms.items()},
+            "best_new_vs_old": round(min(ms["old"]) / min(ms["new"]), 4),
             "median_new_vs_old": round(sorted(ms["old"])[rounds // 2] / sorted(ms["new"])[rounds // 2], 4)}
 
 
@@ -87,7 +96,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--extra", nargs="*", default=[], help="name=path of more builds to compare")
     ap.add_argument("--old", default="build/ab/libmd5hip_old.so", help="the baseline build")
-    ap.add_argument("--only", default="", help="comma list of workloads (c2,ctx,ragged16,c3k3_balanced,c3k6_balanced,c3_hybrid)")
+    ap.add_argument("--only", default="", help="comma list of workloads (see the module docstring)")
     a = ap.parse_args()
     only = set(a.only.split(",")) if a.only else None
     libs = {"old": load(os.path.join(REPO, a.old))}
@@ -103,8 +112,11 @@ def main():
     # ctx: 1 M contexts x 16 KiB (one update launch; contexts re-initialised per run)
     if only is None or "ctx" in only:
         ctx_ab(libs, st, res, a.rounds)
-    if only is None or "ragged16" in only:
-        ragged_ab(libs, st, res, a.rounds)
+    for name, var in (("ragged16", 4), ("ragged16_lines", 7)):
+        if only is None or name in only:
+            ragged_ab(libs, st, res, a.rounds, name, var)
+    if only is None or only & set(FIXED_MORE):
+        fixed_more_ab(libs, st, res, a.rounds, only)
     for K, name, var in ((3, "c3k3_balanced", 5), (6, "c3k6_balanced", 5), (1, "c3_hybrid", 3)):
         if only is None or name in only:
             c3_ab(libs, st, res, a.rounds, K, name, var)
@@ -142,8 +154,46 @@ def ctx_ab(libs, st, res, rounds):
     torch.cuda.empty_cache()
 
 
-def ragged_ab(libs, st, res, rounds):
-    """ragged netcache blocks packed at 16 B (descriptor XDMA)"""
+FIXED_MORE = ("crc_fixed", "crc_fast128", "crc_fast4096", "md5crc32_fixed", "small_fed")
+
+
+def fixed_more_ab(libs, st, res, rounds, only):
+    """The other fixed-length kernels on bench.py's 1,048,576 x 16 KiB: whole-chunk
+    CRC-32 (crc32_fixed_xdma16), fastcrc 128 (crc32_fast_pipe) and 4096
+    (crc32_fast_xdma16), MD5 + CRC-32 records (md5crc32_fixed_xdma16), and a
+    4,096-chunk MD5 batch that AUTO sends to fed pairs (md5_desc_fed; 20
+    launches per sample, ms per launch)."""
+    n, L = 1 << 20, 16384
+    data = m.arena_empty(n * L)
+    m.fill_synthetic(data, seed=0xC2)
+    out = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
+    d, o = data.data_ptr(), out.data_ptr()
+
+    def fed20(Lb):
+        rc = 0
+        for _ in range(20):
+            rc = rc or Lb.md5hip_digest_fixed_variant(d, 4096, L, L, o, st, 0)
+        return rc
+    runs = {"crc_fixed": lambda Lb: Lb.crc32hip_fixed_variant(d, n, L, L, 0, o, st, 0),
+            "crc_fast128": lambda Lb: Lb.crc32hip_fixed_variant(d, n, L, L, 128, o, st, 0),
+            "crc_fast4096": lambda Lb: Lb.crc32hip_fixed_variant(d, n, L, L, 4096, o, st, 0),
+            "md5crc32_fixed": lambda Lb: Lb.md5crc32hip_fixed(d, n, L, L, o, st),
+            "small_fed": fed20}
+    for name in FIXED_MORE:
+        if only is not None and name not in only:
+            continue
+        out.zero_()
+        res[name] = ab(libs, runs[name], lambda: out, rounds)
+        if name == "small_fed":
+            res[name]["ms"] = {k: [round(x / 20, 5) for x in v] for k, v in res[name]["ms"].items()}
+            res[name]["median_ms"] = {k: round(x / 20, 5) for k, x in res[name]["median_ms"].items()}
+        print(json.dumps({name: res[name]}), flush=True)
+    del data, out
+    torch.cuda.empty_cache()
+
+
+def ragged_ab(libs, st, res, rounds, name="ragged16", var=4):
+    """ragged netcache blocks packed at 16 B (descriptor XDMA, or LINES: var 7)"""
     rng = np.random.default_rng(5)
     S, nb = 16384, 983040                       # ~15 GiB
     bl = np.full(nb, S, dtype=np.int64)
@@ -158,9 +208,9 @@ def ragged_ab(libs, st, res, rounds):
     dR = torch.from_numpy(order.astype(np.int32)).cuda()
     dig = torch.empty((nb, 16), dtype=torch.uint8, device="cuda")
     run_r = lambda Lb: Lb.md5hip_digest_desc_variant(arena.data_ptr(), dO.data_ptr(), dL.data_ptr(),  # noqa
-                                                     dR.data_ptr(), nb, dig.data_ptr(), st, 4)
-    res["ragged16"] = ab(libs, run_r, lambda: dig, rounds)
-    print(json.dumps({"ragged16": res["ragged16"]}), flush=True)
+                                                     dR.data_ptr(), nb, dig.data_ptr(), st, var)
+    res[name] = ab(libs, run_r, lambda: dig, rounds)
+    print(json.dumps({name: res[name]}), flush=True)
     del arena, dO, dL, dR, dig
     torch.cuda.empty_cache()
 

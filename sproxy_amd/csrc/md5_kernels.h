@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "hashers.h"
 #include "md5_core.h"
@@ -78,49 +79,67 @@ __device__ __forceinline__ void ring_steps(H& h, typename H::State& st, uint4 (&
   }
 }
 
-__global__ void __launch_bounds__(256)
-md5_fixed_direct(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uint64_t stride,
-                 uint4* __restrict__ out) {
-  using H = Md5Hasher<false>;
-  constexpr int D = 2;
-  H h;
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint8_t* chunk = base + i * stride;
-  const uint4* p = reinterpret_cast<const uint4*>(chunk);
-  const uint32_t nfull = len >> 6;
-  H::State st = h.init();
+// The nfull whole blocks at p (16-B aligned) through a D-deep register ring.
+// Prefetch indices are clamped to the last block so every load is
+// unconditional (no phi copies); the <= D re-reads at the end hit in L1/L2.
+template <class H, int D, bool kPair>
+__device__ __forceinline__ void ring_range(H& h, typename H::State& st, const uint4* p,
+                                           uint32_t nfull) {
   if (nfull) {
-    // D-deep register ring.  Prefetch indices are clamped to the last block so
-    // every load is unconditional (no phi copies); the <= D re-reads at the end
-    // hit in L1/L2.
     const uint32_t lastb = nfull - 1;
     uint4 R[D][4];
 #pragma unroll
     for (int j = 0; j < D; ++j) load_block(R[j], p + 4 * min((uint32_t)j, lastb));
     uint32_t blk = 0;
     for (; blk + D <= nfull; blk += D)     // steady state: no conditionals, so
-      ring_steps<H, D, false>(h, st, R, p, blk, lastb);   // the waits stay counted
+      ring_steps<H, D, kPair>(h, st, R, p, blk, lastb);   // the waits stay counted
 #pragma unroll
     for (int j = 0; j < D - 1; ++j)
       if (blk + j < nfull) h.block(st, R[j]);
   }
+}
+
+__global__ void __launch_bounds__(256)
+md5_fixed_direct(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uint64_t stride,
+                 uint4* __restrict__ out) {
+  using H = Md5Hasher<false>;
+  H h;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* chunk = base + i * stride;
+  const uint32_t nfull = len >> 6;
+  H::State st = h.init();
+  ring_range<H, 2, false>(h, st, reinterpret_cast<const uint4*>(chunk), nfull);
   h.finish(st, chunk + ((uint64_t)nfull << 6), len & 63u, len);
   h.store(out, i, st);
 }
 
 // ---------------------------------------------------------------------------
 // Fixed-length, xpose image filled by LDS-DMA ("xdma"; the default).
-// The same 8 chunks x 128 B wave-instructions and the same LDS image layout
-// as the xpose kernels (lane-linear destination = row r*8 + lane/8, slot
-// lane%8 holding part (lane%8) ^ ((row>>1)&7)), but issued as
-// buffer_load_dwordx4 ... lds: the data skips the VGPRs and the 8
-// ds_write_b128 per stage.  One 8 KiB image per wave: once this lane's
-// ds_reads of stage s have returned, the DMA of stage s+1 is issued and runs
-// under stage s's compression.  The kernel is power-bound, so
-// the saved instructions and register traffic buy clock: 1.7 % faster.
+// A wave-instruction reads 8 chunks x 128 B into the wave's LDS image
+// (lane-linear destination = row r*8 + lane/8, slot lane%8 holding part
+// (lane%8) ^ ((row>>1)&7)), issued as buffer_load_dwordx4 ... lds: the data
+// skips the VGPRs and a ds_write_b128 per row and stage.  One 8 KiB image
+// per wave: once this lane's ds_reads of stage s have returned, the DMA of
+// stage s+1 is issued and runs under stage s's compression.  The kernel is
+// power-bound, so the saved instructions and register traffic
+// buy clock: 1.7 % faster.
 // Requires 64 * stride < 2^31 (checked by the launcher).
 // ---------------------------------------------------------------------------
+// A lane's 128-B row out of an image, as two blocks.  Piece q of the row sits
+// piece_off(q, g) bytes into the lane's image row, g = (lane >> 1) & 7 (the
+// source swizzle undone); at(q) is piece q's address, generic or LDS.
+__device__ __forceinline__ uint32_t piece_off(uint32_t q, uint32_t g) { return (q ^ g) * 16; }
+
+template <class At>
+__device__ __forceinline__ void read_row(uint4 (&w)[2][4], At at) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const u32x4 v = *at(q);
+    w[q >> 2][q & 3] = make_uint4(v.x, v.y, v.z, v.w);
+  }
+}
+
 // xdma_group: one wave hashes the 64-chunk group starting at wave_first (< n)
 // through its 8 KiB image `img`; the hasher is set up by the caller.
 template <class H>
@@ -160,11 +179,9 @@ __device__ __forceinline__ void xdma_group(H& h, const uint8_t* __restrict__ bas
       // wait explicitly; exactly one stage is in flight here
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       uint4 w[2][4];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(img + lane * 128 + ((q ^ g) * 16));
-        w[q >> 2][q & 3] = make_uint4(v.x, v.y, v.z, v.w);
-      }
+      read_row(w, [&](int q) __attribute__((always_inline)) {
+        return reinterpret_cast<const u32x4*>(img + lane * 128 + piece_off(q, g));
+      });
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads done before the refill
       if (stg + 1 < nstage) issue(stg + 1);
       __builtin_amdgcn_sched_barrier(0);
@@ -244,19 +261,7 @@ __device__ __forceinline__ void lane_range(H& h, typename H::State& st, const ui
                                            uint32_t len) {
   const uint32_t nfull = len >> 6;
   if (((uintptr_t)chunk & 15u) == 0) {
-    const uint4* p = reinterpret_cast<const uint4*>(chunk);
-    if (nfull) {
-      const uint32_t lastb = nfull - 1;
-      uint4 R[D][4];
-#pragma unroll
-      for (int j = 0; j < D; ++j) load_block(R[j], p + 4 * min((uint32_t)j, lastb));
-      uint32_t blk = 0;
-      for (; blk + D <= nfull; blk += D)
-        ring_steps<H, D, kPair>(h, st, R, p, blk, lastb);
-#pragma unroll
-      for (int j = 0; j < D - 1; ++j)
-        if (blk + j < nfull) h.block(st, R[j]);
-    }
+    ring_range<H, D, kPair>(h, st, reinterpret_cast<const uint4*>(chunk), nfull);
   } else {
     for (uint32_t blk = 0; blk < nfull; ++blk) {
       uint4 w[4];
@@ -267,34 +272,159 @@ __device__ __forceinline__ void lane_range(H& h, typename H::State& st, const ui
   h.finish(st, chunk + ((uint64_t)nfull << 6), len & 63u, len);
 }
 
-// kImplicit: chunk i at base + i*stride with length `flen` (the fixed-length
-// API's fallback for chunk starts that are not 16-B aligned).
+// ---------------------------------------------------------------------------
+// Chunk sources: where chunk c of a batch lies.  Lane i of a launch takes
+// chunk c = index(i), len(c) bytes at off(c) -- relative to the kernel's
+// base, or (kAbs) an absolute address.  kPairXor: see emit.
+// ---------------------------------------------------------------------------
+// (offset, length) arrays, packed onto lanes in `order` when given.
+struct DescArrays {
+  const uint64_t* __restrict__ offs;
+  const uint32_t* __restrict__ lens;
+  const uint32_t* __restrict__ order;
+  static constexpr bool kPairXor = false;
+  static constexpr bool kAbs = false;          // off() is relative to base
+  __device__ __forceinline__ uint64_t index(uint64_t i) const { return order ? (uint64_t)order[i] : i; }
+  __device__ __forceinline__ uint64_t off(uint64_t c) const { return offs[c]; }
+  __device__ __forceinline__ uint32_t len(uint64_t c) const { return lens[c]; }
+};
+
+// Fixed-length chunks: chunk i at i * stride, flen bytes (the fixed-length
+// API with a base or stride off the 16-B grid, a stride past xdma_group's
+// 32-bit offsets, or a small batch).
+struct FixedChunks {
+  uint64_t stride;
+  uint32_t flen;
+  static constexpr bool kPairXor = false;
+  static constexpr bool kAbs = false;
+  __device__ __forceinline__ uint64_t index(uint64_t i) const { return i; }
+  __device__ __forceinline__ uint64_t off(uint64_t c) const { return c * stride; }
+  __device__ __forceinline__ uint32_t len(uint64_t) const { return flen; }
+};
+
+// The source of a kernel that serves both APIs with one parameter list:
+// kImplicit takes (stride, flen) as FixedChunks and leaves offs, lens and
+// order unused; otherwise DescArrays.
+template <bool kImplicit>
+__device__ __forceinline__ auto chunk_source(const uint64_t* __restrict__ offs,
+                                             const uint32_t* __restrict__ lens,
+                                             const uint32_t* __restrict__ order, uint64_t stride,
+                                             uint32_t flen) {
+  if constexpr (kImplicit) return FixedChunks{stride, flen};
+  else return DescArrays{offs, lens, order};
+}
+
+// The chunks of the fastcrc kernels, which serve both APIs from one
+// instantiation: DescArrays' in launch order, or (offs == nullptr)
+// FixedChunks'.  (One instantiation per API doubles those kernels' code, and
+// crc32_fast_pipe then ran 6-9 % slower: profiles/loader_split/.)
+struct EitherChunks {
+  DescArrays arrays;
+  FixedChunks fixed;
+  __device__ __forceinline__ uint64_t off(uint64_t k) const { return arrays.offs ? arrays.off(k) : fixed.off(k); }
+  __device__ __forceinline__ uint32_t len(uint64_t k) const { return arrays.offs ? arrays.len(k) : fixed.len(k); }
+};
+
+// blk_make_crc's fastcrc windows (blk_io.c:408-424) over an inner source's
+// chunks, as a batch of 2n rows: row 2k = the first F bytes of chunk k, row
+// 2k+1 = its last F bytes; a chunk of <= F bytes is row 2k alone (row 2k+1
+// empty: CRC 0, the XOR identity).  kPairXor: lanes 2k and 2k+1 combine,
+// out[k] = crc ^ crc.
+struct FastWindows {
+  EitherChunks chunks;
+  uint32_t F;
+  static constexpr bool kPairXor = true;
+  static constexpr bool kAbs = false;
+  __device__ __forceinline__ uint64_t index(uint64_t i) const { return i; }
+  __device__ __forceinline__ uint64_t off(uint64_t c) const {
+    const uint64_t k = c >> 1;
+    const uint64_t o = chunks.off(k);
+    const uint32_t L = chunks.len(k);
+    return ((c & 1u) && L > F) ? o + (L - F) : o;
+  }
+  __device__ __forceinline__ uint32_t len(uint64_t c) const {
+    const uint32_t L = chunks.len(c >> 1);
+    return L <= F ? ((c & 1u) ? 0u : L) : F;
+  }
+};
+
+// A finished lane's digest: stored at c, or (kPairXor) XORed with its pair
+// lane and stored by the even lane at c / 2.  Pairs are live together.
+template <class Src, class H>
+__device__ __forceinline__ void emit(H& h, typename H::Out* __restrict__ out, uint64_t c,
+                                     const typename H::State& st) {
+  if constexpr (Src::kPairXor) {
+    const uint32_t v = st.c ^ (uint32_t)__shfl_xor((int)st.c, 1, 64);
+    if (!(c & 1u)) out[c >> 1] = v;
+  } else {
+    h.store(out, c, st);
+  }
+}
+
+// The address of a source's off().  kAbs: base is unused (offsetting a null
+// base would be undefined); otherwise base + offset stays a global pointer
+// (no flat loads).
+template <bool kAbs>
+__device__ __forceinline__ const uint8_t* chunk_at(const uint8_t* __restrict__ base, uint64_t off) {
+  return kAbs ? reinterpret_cast<const uint8_t*>((uintptr_t)off) : base + off;
+}
+
+// A lane's place in the 64-row group whose first position is `first` (< n):
+// its chunk c, where it lies and how long it is.  Lanes past n are not live:
+// they alias the group's first row (an address that is in bounds) with
+// length 0.
+struct GroupLane {
+  uint64_t c, off;
+  const uint8_t* chunk;
+  uint32_t len, nfull;
+  bool live;
+  // wave-uniform: some live chunk does not start on the 16-B grid
+  __device__ __forceinline__ bool any_unaligned() const {
+    return __ballot(live && (((uintptr_t)chunk & 15u) != 0)) != 0;
+  }
+};
+
+template <class Src>
+__device__ __forceinline__ GroupLane group_lane(const Src& src, const uint8_t* __restrict__ base,
+                                                uint64_t n, uint64_t first) {
+  GroupLane g;
+  const uint64_t i = first + (threadIdx.x & 63u);
+  g.live = i < n;
+  g.c = src.index(g.live ? i : first);
+  g.off = src.off(g.c);
+  g.chunk = chunk_at<Src::kAbs>(base, g.off);
+  g.len = g.live ? src.len(g.c) : 0u;
+  g.nfull = g.len >> 6;
+  return g;
+}
+
 // Waves holding long chunks raise their issue priority, so the longest serial
 // chains -- which bound a mixed batch -- progress at their latency limit while
-// short-chunk waves fill the remaining issue slots.
+// short-chunk waves fill the remaining issue slots.  bmax: the wave's longest
+// chain in 64-B blocks.
+__device__ __forceinline__ void chain_prio(uint32_t bmax) {
+  if (bmax >= 4096u) __builtin_amdgcn_s_setprio(3);        // >= 256 KiB
+  else if (bmax >= 1024u) __builtin_amdgcn_s_setprio(2);   // >= 64 KiB
+  else if (bmax >= 256u) __builtin_amdgcn_s_setprio(1);    // >= 16 KiB
+  else __builtin_amdgcn_s_setprio(0);                      // (a persistent wave's previous group)
+}
+
+// One lane per chunk, lane-direct (any alignment).
 // D: depth of the per-lane register ring (blocks in flight per lane).  Mixed
 // batches have few waves per SIMD (C3: ~1.2), so latency must be hidden by
 // prefetch depth, not by occupancy.
-template <bool kImplicit, class H, int D>
-__device__ __forceinline__ void desc_body(const uint8_t* __restrict__ base,
-                                          const uint64_t* __restrict__ offs,
-                                          const uint32_t* __restrict__ lens,
-                                          const uint32_t* __restrict__ order, uint64_t n,
-                                          uint64_t stride, uint32_t flen,
+template <class H, int D, class Src>
+__device__ __forceinline__ void desc_body(const uint8_t* __restrict__ base, const Src& src, uint64_t n,
                                           typename H::Out* __restrict__ out,
                                           uint8_t* hlds = nullptr) {
   H h;
   h.setup(hlds);                     // before any early exit (may barrier)
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint64_t c = (!kImplicit && order) ? (uint64_t)order[i] : i;
-  const uint8_t* chunk = base + (kImplicit ? c * stride : offs[c]);
-  const uint32_t len = kImplicit ? flen : lens[c];
-  const uint32_t nfull = len >> 6;
-  const uint32_t wmax = wave_max(nfull);
-  if (wmax >= 4096u) __builtin_amdgcn_s_setprio(3);        // >= 256 KiB
-  else if (wmax >= 1024u) __builtin_amdgcn_s_setprio(2);   // >= 64 KiB
-  else if (wmax >= 256u) __builtin_amdgcn_s_setprio(1);    // >= 16 KiB
+  const uint64_t c = src.index(i);
+  const uint8_t* chunk = chunk_at<Src::kAbs>(base, src.off(c));
+  const uint32_t len = src.len(c);
+  chain_prio(wave_max(len >> 6));
   typename H::State st = h.init();
   lane_range<H, D>(h, st, chunk, len);
   h.store(out, c, st);
@@ -306,7 +436,7 @@ __global__ void __launch_bounds__(256)
 md5_desc(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
          const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order, uint64_t n,
          uint64_t stride, uint32_t flen, uint4* __restrict__ out) {
-  desc_body<kImplicit, Md5Hasher<true>, 8>(base, offs, lens, order, n, stride, flen, out);
+  desc_body<Md5Hasher<true>, 8>(base, chunk_source<kImplicit>(offs, lens, order, stride, flen), n, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -324,8 +454,6 @@ md5_desc(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
 // with a chunk start that is not 16-B aligned takes the lane-direct path
 // (lane_range).  One wave per workgroup, as md5_desc: the dispatcher spreads
 // long-chunk waves one per CU, and s_setprio favours them.
-// desc_xpose_group: one wave hashes the 64-chunk group whose first position
-// in `order` is `first` (< n); the hasher is set up by the caller.
 // ---------------------------------------------------------------------------
 // kLong > 0: the first `nlong` waves (one per CU; with longest-first order
 // these hold the batch's longest chunks) take the lane-direct path with an
@@ -356,410 +484,352 @@ __device__ __forceinline__ bool long_outlier(const uint32_t* __restrict__ lens,
 // 64-B blocks (256 KiB)
 constexpr uint32_t kHybridLongBlocks = MD5HIP_HYBRID_LONG_BLOCKS;
 
-// Where chunk i of a descriptor batch lies: (offset, length) arrays, packed
-// onto lanes in `order` when given.
-struct DescArrays {
-  const uint64_t* __restrict__ offs;
-  const uint32_t* __restrict__ lens;
-  const uint32_t* __restrict__ order;
-  static constexpr bool kPairXor = false;
-  static constexpr bool kAbs = false;          // off() is relative to base
-  __device__ __forceinline__ uint64_t index(uint64_t i) const { return order ? (uint64_t)order[i] : i; }
-  __device__ __forceinline__ uint64_t off(uint64_t c) const { return offs[c]; }
-  __device__ __forceinline__ uint32_t len(uint64_t c) const { return lens[c]; }
+// f(C) for the constants C (indices that must fold into immediates); the
+// eight wave-instructions of a stage.
+template <class F, int... C>
+__device__ __forceinline__ void each_const(F f, std::integer_sequence<int, C...>) {
+  (f(std::integral_constant<int, C>{}), ...);
+}
+template <class F>
+__device__ __forceinline__ void each_row(F f) { each_const(f, std::make_integer_sequence<int, 8>{}); }
+
+using lds_u8 = __attribute__((address_space(3))) uint8_t;
+using lds_u4 = const __attribute__((address_space(3))) u32x4;
+
+// What a wave's LDS-DMA reads for its group.  Wave-instruction r fills image
+// rows r*8 .. r*8+7, 8 lanes per row: rptr[r] is this lane's 16-B part
+// (source swizzle) of stage 0 of row r*8 + lane/8, rlast[r] that row's last
+// stage.  Until the first row runs out (stage rmin), no row's stage index is
+// clamped and the stage offset is wave-uniform: one 64-bit add per row with
+// the offset in SGPRs instead of min + shift + add (16 VALU fewer per 128-B
+// stage, ~2.5 % of the stage's VALU).
+struct RowSet {
+  const uint8_t* rptr[8];
+  uint32_t rlast[8];
+  uint32_t rmin;
+  uint32_t smax, nst;        // the wave's most 128-B stages, this lane's
+  uint32_t g;                // this lane's read swizzle (piece_off)
+  // the image as an LDS pointer once: a generic pointer per DMA costs a
+  // null-check select (2 SALU) per row and stage
+  lds_u8* limg;
 };
 
-// blk_make_crc's fastcrc windows (blk_io.c:408-424) as a descriptor batch of
-// 2n rows: row 2k = the first F bytes of chunk k, row 2k+1 = its last F
-// bytes; a chunk of <= F bytes is row 2k alone (row 2k+1 empty: CRC 0, the
-// XOR identity).  kPairXor: lanes 2k and 2k+1 combine, out[k] = crc ^ crc.
-// Chunk k at offs[k] / lens[k], or (offs == nullptr) at k * stride, flen.
-struct FastWindows {
-  const uint64_t* __restrict__ offs;
-  const uint32_t* __restrict__ lens;
-  uint64_t stride;
-  uint32_t flen, F;
-  static constexpr bool kPairXor = true;
-  static constexpr bool kAbs = false;
-  __device__ __forceinline__ uint64_t index(uint64_t i) const { return i; }
-  __device__ __forceinline__ uint32_t clen(uint64_t k) const { return offs ? lens[k] : flen; }
-  __device__ __forceinline__ uint64_t off(uint64_t c) const {
-    const uint64_t k = c >> 1;
-    const uint64_t o = offs ? offs[k] : k * stride;
-    const uint32_t L = clen(k);
-    return ((c & 1u) && L > F) ? o + (L - F) : o;
+// The rows of a group with smax > 0.  `addr` is this lane's chunk start: its
+// offset from base, or (kAbs) its address.  A row's stage index is clamped to
+// its own last stage; rows without any 128-B stage re-read the wave's longest
+// chunk (always in bounds).
+// kLines: the rows are the 128-B lines the chunks lie in, from each chunk's
+// line-aligned start (addr is an address); a row that starts off the line
+// has one line more than it has stages.
+template <bool kAbs, bool kLines = false>
+__device__ __forceinline__ RowSet row_set(const uint8_t* __restrict__ base, uint64_t addr,
+                                          uint32_t nst, uint32_t smax, uint8_t* img) {
+  static_assert(kAbs || !kLines, "lines are aligned by address");
+  const uint32_t lane = threadIdx.x & 63u;
+  RowSet rs;
+  // the row with the most stages stands in for rows without any
+  const uint32_t mrow = __builtin_ctzll(__ballot(nst == smax));
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    uint32_t row = (uint32_t)r * 8u + (lane >> 3);
+    const uint32_t rn = (uint32_t)__shfl((int)nst, (int)row, 64);
+    if (rn == 0) row = mrow;
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)addr, (int)row, 64);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(addr >> 32), (int)row, 64);
+    const uint32_t part = (lane & 7u) ^ ((row >> 1) & 7u);      // source swizzle
+    const uint64_t ra = (((uint64_t)hi << 32) | (kLines ? lo & ~127u : lo)) + part * 16u;
+    rs.rptr[r] = chunk_at<kAbs>(base, ra);
+    rs.rlast[r] = (rn ? rn : smax) - 1u + (kLines ? (uint32_t)((lo & 127u) != 0u) : 0u);
   }
-  __device__ __forceinline__ uint32_t len(uint64_t c) const {
-    const uint32_t L = clen(c >> 1);
-    return L <= F ? ((c & 1u) ? 0u : L) : F;
-  }
-};
+  rs.rmin = wave_min(nst ? nst : smax) - 1u;
+  rs.smax = smax;
+  rs.nst = nst;
+  rs.g = (lane >> 1) & 7u;
+  rs.limg = (lds_u8*)img;
+  return rs;
+}
 
-// A finished lane's digest: stored at c, or (kPairXor) XORed with its pair
-// lane and stored by the even lane at c / 2.  Pairs are live together.
-template <class Src, class H>
-__device__ __forceinline__ void emit(H& h, typename H::Out* __restrict__ out, uint64_t c,
-                                     const typename H::State& st) {
-  if constexpr (Src::kPairXor) {
-    const uint32_t v = st.c ^ (uint32_t)__shfl_xor((int)st.c, 1, 64);
-    if (!(c & 1u)) out[c >> 1] = v;
+// Stage (line) stg of every row into the one image, cache policy P.
+template <int P>
+__device__ __forceinline__ void issue_rows(const RowSet& rs, uint32_t stg) {
+  if (stg <= rs.rmin) {                                  // wave-uniform, no row clamped
+    const uint64_t so = (uint64_t)stg << 7;
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+      __builtin_amdgcn_global_load_lds(rs.rptr[r] + so, rs.limg + r * 1024, 16, 0, P);
   } else {
-    h.store(out, c, st);
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+      __builtin_amdgcn_global_load_lds(rs.rptr[r] + (min(stg, rs.rlast[r]) << 7), rs.limg + r * 1024,
+                                       16, 0, P);
   }
 }
 
+// Loader 1 of 3, one image: the DMA of stage s+1 is issued once this wave's
+// row reads of stage s have returned, and runs under stage s's compression; a
+// lane compresses a stage only while it still has one.
+template <int P, class H>
+__device__ __forceinline__ void run_stages(H& h, typename H::State& st, const RowSet& rs) {
+  lds_u8* myrow = rs.limg + (threadIdx.x & 63u) * 128u;
+  issue_rows<P>(rs, 0);
+  for (uint32_t stg = 0; stg < rs.smax; ++stg) {
+    // hipcc does not order ds_read after an LDS-DMA into the same bytes
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    uint4 w[2][4];
+    read_row(w, [&](int q) __attribute__((always_inline)) {
+      return reinterpret_cast<lds_u4*>(myrow + piece_off(q, rs.g));
+    });
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads done before the refill
+    if (stg + 1 < rs.smax) issue_rows<P>(rs, stg + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (stg < rs.nst) {
+      h.block(st, w[0]);
+      h.block(st, w[1]);
+    }
+  }
+}
+
+// Loader 2 of 3, two 8 KiB images for a LONE wave on its SIMD (BALANCED): a
+// lone wave issues one instruction per slot, so everything it does besides
+// VALU comes straight off its chain.  Per 128-B stage: the next stage's
+// DMA goes into the other image BEFORE this stage's rows are read (so
+// the ds_read latency is spent issuing it, not waiting), block 0 starts
+// as soon as its four rows are in (lgkmcnt(4)), and the DMA's LDS base
+// is set twice per stage, not eight times: rows 0-3 / 4-7 take M0 =
+// image / image + 4 KiB and their 1 KiB row offset in the instruction
+// (which adds it to the global address too, so the row pointers are
+// pre-biased by it).  The DMA lead stays one stage, as with one image:
+// a third image for a two-stage lead (the 96 KiB a CU already reserves
+// for BALANCED) measured 1.0-1.4 % slower on 3 and 6 coalesced C3
+// batches (profiles/r04h/balanced3_ab.json).
+// live: this lane holds a chunk of the batch.
+template <int P, class H>
+__device__ __forceinline__ void run_stages2(H& h, typename H::State& st, const RowSet& rs, bool live) {
+  const uint32_t nst = rs.nst, smax = rs.smax, rmin = rs.rmin;
+  lds_u8* limg = rs.limg;
+  const uint8_t* bptr[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    bptr[r] = rs.rptr[r] - (r & 3) * 1024;
+    asm volatile("" : "+v"(bptr[r]));      // keep the bias in the pointer (not re-added per stage)
+  }
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  // row R's DMA from g + OFF (constants: both go into the instruction's
+  // immediate offset, which the LDS address takes too, so M0 is the row
+  // half's base less OFF)
+  auto dma = [&](auto R, auto OFF, const uint8_t* g, lds_u8* im) __attribute__((always_inline)) {
+    constexpr int r = decltype(R)::value;
+    constexpr int o = decltype(OFF)::value;
+    __builtin_amdgcn_global_load_lds(g, im + (r >> 2) * 4096 - o, 16, (r & 3) * 1024 + o, P);
+  };
+  // stage stg into image B (a template constant: the image bases fold
+  // into M0 values and ds_read offsets, no address arithmetic per stage)
+  auto issue = [&](uint32_t stg, auto B) __attribute__((always_inline)) {
+    auto* im = limg + decltype(B)::value * 8192u;
+    if (stg <= rmin) {                                   // wave-uniform, no row clamped
+      const uint64_t so = (uint64_t)stg << 7;
+      each_row([&](auto R) __attribute__((always_inline)) { dma(R, I0{}, bptr[R] + so, im); });
+    } else {
+      each_row([&](auto R) __attribute__((always_inline)) {
+        dma(R, I0{}, bptr[R] + (min(stg, rs.rlast[R]) << 7), im);
+      });
+    }
+  };
+  // this lane's 8 row-piece addresses in image 0, kept in VGPRs: image
+  // 1's are the same + 8192, an immediate of the ds_read
+  uint32_t raddr[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    raddr[q] = (uint32_t)(uintptr_t)(limg + (threadIdx.x & 63u) * 128u + piece_off(q, rs.g));
+    asm volatile("" : "+v"(raddr[q]));
+  }
+  // One stage held in image B: once it has landed (the only one out) its
+  // rows are read, `next` issues the following stage's DMA into the other
+  // image under the reads' latency, and the lane compresses it (act: it still
+  // has a stage), block 0 as soon as its four rows are in.
+  auto stage = [&](auto B, bool act, auto next) __attribute__((always_inline)) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    uint4 w[2][4];
+    read_row(w, [&](int q) __attribute__((always_inline)) {
+      return reinterpret_cast<lds_u4*>(raddr[q] + decltype(B)::value * 8192u);
+    });
+    next();
+    asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");   // block 0's rows
+    __builtin_amdgcn_sched_barrier(0);
+    if (act) h.block(st, w[0]);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (act) h.block(st, w[1]);
+  };
+  auto guarded = [&](uint32_t stg, auto B) __attribute__((always_inline)) {
+    stage(B, stg < nst, [&]() __attribute__((always_inline)) {
+      if (stg + 1 < smax) issue(stg + 1, std::integral_constant<int, 1 - decltype(B)::value>{});
+    });
+  };
+  // The stages every live lane holds whole, whose next DMAs
+  // clamp no row: no per-lane guard, no clamp test (the common case:
+  // LPT groups are near-uniform), four stages per loop test.  The row
+  // pointers are formed once per four stages (pb = bptr + offset); the
+  // stages' DMAs reach +128 .. +512 through the instruction offset, so
+  // their M0 is the image base less that much (the images sit kImgPad bytes
+  // into the workgroup's LDS, balanced_body).
+  auto quad = [&](const uint8_t* const (&pb)[8], auto J) __attribute__((always_inline)) {
+    constexpr int j = decltype(J)::value;                 // stage j of the quad
+    stage(std::integral_constant<int, (j & 1)>{}, true, [&]() __attribute__((always_inline)) {
+      using O = std::integral_constant<int, 128 * (j + 1)>;   // the next stage: quad + j + 1
+      each_row([&](auto R) __attribute__((always_inline)) {
+        dma(R, O{}, pb[R], limg + ((j & 1) ^ 1) * 8192u);
+      });
+    });
+  };
+  const uint32_t fmin = wave_min(live ? nst : 0xFFFFFFFFu);   // stages every live lane holds
+  const uint32_t lim = min(rmin, fmin - 1u);                 // fmin 0: wraps, guarded below
+  issue(0, I0{});
+  uint32_t stg = 0;
+  if (fmin > 0)
+    for (; stg + 4 <= lim; stg += 4) {
+      const uint8_t* pb[8];
+      const uint64_t so = (uint64_t)stg << 7;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) pb[r] = bptr[r] + so;
+      each_const([&](auto J) __attribute__((always_inline)) { quad(pb, J); },
+                 std::make_integer_sequence<int, 4>{});
+    }
+  for (; stg < smax; stg += 2) {
+    guarded(stg, I0{});
+    if (stg + 1 < smax) guarded(stg + 1, I1{});
+  }
+}
+
+// Loader 3 of 3, whole lines (one image; rows from row_set<true, true>).
+// Row r's line L is the 128-B line L of its chunk's line-aligned base;
+// window k (chunk bytes [128k, 128k + 128)) is line k from piece s on, then
+// line k + 1's first s pieces, s = sh, the chunk's 16-B offset in its line.
+// A lane reads line L rotated by s (piece q of the read = line piece
+// (q + s) & 7), so window k's piece q is line k's read for q + s < 8, line
+// k+1's after.  Lines 0..smax (a row with s > 0 needs line nst; one with
+// s = 0 is clamped to its own last stage).  Default cache policy: lines are
+// shared between rows.
+template <class H>
+__device__ __forceinline__ void run_lines(H& h, typename H::State& st, const RowSet& rs, uint32_t sh) {
+  const uint32_t nst = rs.nst, smax = rs.smax;
+  lds_u8* myrow = rs.limg + (threadIdx.x & 63u) * 128u;
+  auto read_rot = [&](uint4 (&R)[2][4]) __attribute__((always_inline)) {
+    read_row(R, [&](int q) __attribute__((always_inline)) {
+      return reinterpret_cast<lds_u4*>(myrow + piece_off((q + sh) & 7u, rs.g));
+    });
+  };
+  uint4 ra[2][4], rb[2][4];
+  issue_rows<0>(rs, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  read_rot(ra);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  issue_rows<0>(rs, 1);
+  // window k: `cur` (line k) completed in place from `nxt` (line k + 1,
+  // read here; the next window's `cur`)
+  auto step = [&](uint32_t k, uint4 (&cur)[2][4], uint4 (&nxt)[2][4]) __attribute__((always_inline)) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    read_rot(nxt);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads done before the refill
+    if (k + 2 <= smax) issue_rows<0>(rs, k + 2);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if ((uint32_t)q + sh >= 8u) cur[q >> 2][q & 3] = nxt[q >> 2][q & 3];
+    if (k < nst) {
+      h.block(st, cur[0]);
+      h.block(st, cur[1]);
+    }
+  };
+  for (uint32_t k = 0; k < smax; k += 2) {
+    step(k, ra, rb);
+    if (k + 1 < smax) step(k + 1, rb, ra);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// desc_xpose_group: one wave hashes the 64-chunk group whose first position
+// in `order` is `first` (< n); the hasher is set up by the caller.  It places
+// its lanes (group_lane), sends HYBRID's long waves and groups with a chunk
+// off the 16-B grid to lane_range, and otherwise picks one of the three
+// loaders above and its cache policy.
+// ---------------------------------------------------------------------------
 // HYBRID's lane-direct long waves refill their 8-block ring two blocks (one
 // whole 128-B line) at a time, so no lane leaves half a line behind to be
 // fetched again after eviction (ring_steps).
 // NB: LDS-DMA images per wave, 1 or 2.  2 is BALANCED's lone wave per
 // SIMD: the next stage's DMA goes into the other image under this stage's
-// row reads (below).
+// row reads (run_stages2).
 // kShift (one image): a wave holding a chunk that does not start on a
 // 128-B line loads whole LINES instead of chunk-relative 128-B stages, each
-// line once; a lane rotates its line reads by its chunk's 16-B offset s and
-// takes a window's last s pieces from the next line (one line of registers
-// more, 32 v_cndmask per 128 B).  Chunk-relative stages of such a chunk
-// straddle two lines and share one with the next stage, which L2 evicts
-// between the two visits under 16 waves per CU (16-B-packed ragged blocks:
-// 1.29x the payload read from HBM).
+// line once (run_lines); a lane rotates its line reads by its chunk's 16-B
+// offset s and takes a window's last s pieces from the next line (one line
+// of registers more, 32 v_cndmask per 128 B).  Chunk-relative stages of such
+// a chunk straddle two lines and share one with the next stage, which L2
+// evicts between the two visits under 16 waves per CU (16-B-packed ragged
+// blocks: 1.29x the payload read from HBM).
 template <int CP, class H, uint32_t kLong = 0, class Src = DescArrays, int NB = 1,
           bool kShift = false>
 __device__ __forceinline__ void desc_xpose_group(H& h, const uint8_t* __restrict__ base,
                                                  const Src& src, uint64_t n,
                                                  uint64_t first, typename H::Out* __restrict__ out,
                                                  uint8_t* img, uint32_t nlong = 0) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t i = first + lane;
-  const bool live = i < n;
-  const uint64_t c = src.index(live ? i : first);
-  const uint64_t off = src.off(c);
-  const uint8_t* chunk = Src::kAbs ? reinterpret_cast<const uint8_t*>((uintptr_t)off) : base + off;
-  const uint32_t len = live ? src.len(c) : 0u;
-  const uint32_t nfull = len >> 6;
-  const uint32_t nst = nfull >> 1;                       // this lane's 128-B stages
+  static_assert(NB == 1 || NB == 2, "LDS-DMA images per wave: 1 or 2");
+  static_assert(NB == 1 || !kShift, "whole lines load into one image");
+  const GroupLane L = group_lane(src, base, n, first);
+  const uint32_t nst = L.nfull >> 1;                     // this lane's 128-B stages
   const uint32_t smax = wave_max(nst);
-  const uint32_t bmax = wave_max(nfull);
-  if (bmax >= 4096u) __builtin_amdgcn_s_setprio(3);      // as desc_body
-  else if (bmax >= 1024u) __builtin_amdgcn_s_setprio(2);
-  else if (bmax >= 256u) __builtin_amdgcn_s_setprio(1);
-  else __builtin_amdgcn_s_setprio(0);                    // (a persistent wave's previous group)
+  const uint32_t bmax = wave_max(L.nfull);
+  chain_prio(bmax);
   typename H::State st = h.init();
-  const bool unaligned = __ballot(live && (((uintptr_t)chunk & 15u) != 0)) != 0;
+  const bool unaligned = L.any_unaligned();
   if (kLong && bmax >= kLong && (first >> 6) < nlong) {
-    if (live) {
-      lane_range<H, 8, true>(h, st, chunk, len);
-      emit<Src>(h, out, c, st);
+    if (L.live) {
+      lane_range<H, 8, true>(h, st, L.chunk, L.len);
+      emit<Src>(h, out, L.c, st);
     }
     return;
   }
   if (unaligned) {
-    if (live) {                      // rare: a short ring keeps VGPRs for the main path
-      lane_range<H, 2>(h, st, chunk, len);
-      emit<Src>(h, out, c, st);
+    if (L.live) {                    // rare: a short ring keeps VGPRs for the main path
+      lane_range<H, 2>(h, st, L.chunk, L.len);
+      emit<Src>(h, out, L.c, st);
     }
     return;
   }
   if (smax) {
-    // the row with the most stages stands in for rows without any
-    const uint32_t mrow = __builtin_ctzll(__ballot(nst == smax));
-    const uint8_t* rptr[8];            // base + offset: stays a global pointer (no flat loads)
-    uint32_t rlast[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      uint32_t row = (uint32_t)r * 8u + (lane >> 3);
-      const uint32_t rn = (uint32_t)__shfl((int)nst, (int)row, 64);
-      if (rn == 0) row = mrow;
-      const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)off, (int)row, 64);
-      const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(off >> 32), (int)row, 64);
-      const uint32_t part = (lane & 7u) ^ ((row >> 1) & 7u);      // source swizzle (xpose)
-      const uint64_t ra = (((uint64_t)hi << 32) | lo) + part * 16u;
-      rptr[r] = Src::kAbs ? reinterpret_cast<const uint8_t*>((uintptr_t)ra) : base + ra;
-      rlast[r] = (rn ? rn : smax) - 1u;
-    }
-    const uint32_t g = (lane >> 1) & 7u;
-    const uint8_t* myrow = img + lane * 128u;
-    auto read_row = [&](uint4 (&w)[2][4]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(myrow + ((q ^ g) * 16));
-        w[q >> 2][q & 3] = make_uint4(v.x, v.y, v.z, v.w);
-      }
-    };
-    static_assert(NB == 1 || NB == 2, "LDS-DMA images per wave: 1 or 2");
-    if constexpr (NB == 2) {
-      // Two 8 KiB images for a LONE wave on its SIMD (BALANCED): a lone
-      // wave issues one instruction per slot, so everything it does besides
-      // VALU comes straight off its chain.  Per 128-B stage: the next stage's
-      // DMA goes into the other image BEFORE this stage's rows are read (so
-      // the ds_read latency is spent issuing it, not waiting), block 0 starts
-      // as soon as its four rows are in (lgkmcnt(4)), and the DMA's LDS base
-      // is set twice per stage, not eight times: rows 0-3 / 4-7 take M0 =
-      // image / image + 4 KiB and their 1 KiB row offset in the instruction
-      // (which adds it to the global address too, so the row pointers are
-      // pre-biased by it).  The DMA lead stays one stage, as with one image:
-      // a third image for a two-stage lead (the 96 KiB a CU already reserves
-      // for BALANCED) measured 1.0-1.4 % slower on 3 and 6 coalesced C3
-      // batches (profiles/r04h/balanced3_ab.json).
-      const bool lined = __ballot(((uint32_t)(uintptr_t)chunk & 127u) != 0 && live && nst != 0) == 0;
-      const uint32_t rmin = wave_min(nst ? nst : smax) - 1u;
-      auto* limg = (__attribute__((address_space(3))) uint8_t*)img;
-      const uint8_t* bptr[8];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        bptr[r] = rptr[r] - (r & 3) * 1024;
-        asm volatile("" : "+v"(bptr[r]));      // keep the bias in the pointer (not re-added per stage)
-      }
-      auto run2 = [&](auto pol) __attribute__((always_inline)) {
-        constexpr int P = decltype(pol)::value;
-        // row R's DMA (the offset must be an immediate: R is a template constant)
-        auto dma = [&](auto R, const uint8_t* g, __attribute__((address_space(3))) uint8_t* im)
-            __attribute__((always_inline)) {
-          constexpr int r = decltype(R)::value;
-          __builtin_amdgcn_global_load_lds(g, im + (r >> 2) * 4096, 16, (r & 3) * 1024, P);
-        };
-        // stage stg into image B (a template constant: the image bases fold
-        // into M0 values and ds_read offsets, no address arithmetic per stage)
-        auto issue = [&](uint32_t stg, auto B) __attribute__((always_inline)) {
-          auto* im = limg + decltype(B)::value * 8192u;
-          auto rows = [&](auto... R) __attribute__((always_inline)) {
-            if (stg <= rmin) {                                 // wave-uniform, no row clamped
-              const uint64_t so = (uint64_t)stg << 7;
-              (dma(R, bptr[decltype(R)::value] + so, im), ...);
-            } else {
-              (dma(R, bptr[decltype(R)::value] + (min(stg, rlast[decltype(R)::value]) << 7), im), ...);
-            }
-          };
-          rows(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{},
-               std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{},
-               std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{},
-               std::integral_constant<int, 6>{}, std::integral_constant<int, 7>{});
-        };
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        // this lane's 8 row-piece addresses in image 0, kept in VGPRs: image
-        // 1's are the same + 8192, an immediate of the ds_read
-        using lds_u4 = const __attribute__((address_space(3))) u32x4;
-        uint32_t raddr[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          raddr[q] = (uint32_t)(uintptr_t)(limg + (myrow - img) + ((q ^ g) * 16));
-          asm volatile("" : "+v"(raddr[q]));
-        }
-        // one stage held in image B; the next goes into the other one
-        auto stage = [&](uint32_t stg, auto B) __attribute__((always_inline)) {
-          constexpr int b = decltype(B)::value;
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // stage stg landed (the only one out)
-          uint4 w[2][4];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const u32x4 v = *reinterpret_cast<lds_u4*>(raddr[q] + b * 8192u);
-            w[q >> 2][q & 3] = make_uint4(v.x, v.y, v.z, v.w);
-          }
-          if (stg + 1 < smax) {                                  // issued under the reads' latency
-            if constexpr (b == 0) issue(stg + 1, I1{});
-            else issue(stg + 1, I0{});
-          }
-          asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");   // block 0's rows
-          __builtin_amdgcn_sched_barrier(0);
-          if (stg < nst) h.block(st, w[0]);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          if (stg < nst) h.block(st, w[1]);
-        };
-        // The stages every live lane holds whole, whose next DMAs
-        // clamp no row: no per-lane guard, no clamp test (the common case:
-        // LPT groups are near-uniform), four stages per loop test.  The row
-        // pointers are formed once per four stages (pb = bptr + offset); the
-        // stages' DMAs reach +128 .. +512 through the instruction offset,
-        // which the LDS address takes too, so their M0 is the image base less
-        // that much (the images sit kImgPad bytes into the workgroup's LDS,
-        // balanced_body).
-        auto dma_at = [&](auto R, auto OFF, const uint8_t* g, __attribute__((address_space(3))) uint8_t* im)
-            __attribute__((always_inline)) {
-          constexpr int r = decltype(R)::value;
-          constexpr int o = decltype(OFF)::value;
-          __builtin_amdgcn_global_load_lds(g, im + (r >> 2) * 4096 - o, 16, (r & 3) * 1024 + o, P);
-        };
-        auto stage_all = [&](const uint8_t* const (&pb)[8], auto J) __attribute__((always_inline)) {
-          constexpr int j = decltype(J)::value;                 // stage j of the quad
-          constexpr int b = j & 1;
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          uint4 w[2][4];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const u32x4 v = *reinterpret_cast<lds_u4*>(raddr[q] + b * 8192u);
-            w[q >> 2][q & 3] = make_uint4(v.x, v.y, v.z, v.w);
-          }
-          {
-            auto* im = limg + (b ^ 1) * 8192u;
-            using O = std::integral_constant<int, 128 * (j + 1)>;   // the next stage: quad + j + 1
-            auto rows = [&](auto... R) __attribute__((always_inline)) {
-              (dma_at(R, O{}, pb[decltype(R)::value], im), ...);
-            };
-            rows(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{},
-                 std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{},
-                 std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{},
-                 std::integral_constant<int, 6>{}, std::integral_constant<int, 7>{});
-          }
-          asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          h.block(st, w[0]);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          h.block(st, w[1]);
-        };
-        const uint32_t fmin = wave_min(live ? nst : 0xFFFFFFFFu);   // stages every live lane holds
-        const uint32_t lim = min(rmin, fmin - 1u);                 // fmin 0: wraps, guarded below
-        issue(0, I0{});
-        uint32_t stg = 0;
-        if (fmin > 0)
-          for (; stg + 4 <= lim; stg += 4) {
-            const uint8_t* pb[8];
-            const uint64_t so = (uint64_t)stg << 7;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) pb[r] = bptr[r] + so;
-            stage_all(pb, std::integral_constant<int, 0>{});
-            stage_all(pb, std::integral_constant<int, 1>{});
-            stage_all(pb, std::integral_constant<int, 2>{});
-            stage_all(pb, std::integral_constant<int, 3>{});
-          }
-        for (; stg < smax; stg += 2) {
-          stage(stg, I0{});
-          if (stg + 1 < smax) stage(stg + 1, I1{});
-        }
-      };
-      if (CP == 0 || !lined) run2(std::integral_constant<int, 0>{});
-      else run2(std::integral_constant<int, CP>{});
+    // Cache policy per wave: CP (nt for the product kernels) when every
+    // row starts on a 128-B line; otherwise each 128-B stage straddles two
+    // lines and shares one with the row's next stage, and nt loads let that
+    // line leave L2 before the next stage asks for it (16-B-packed ragged
+    // blocks: 1.83x HBM bytes, 1.35x time), so such waves load with the
+    // default policy (profiles/r02_desc_cache_policy_ab.json) -- or, under
+    // kShift, load whole lines.
+    const bool lined =
+        __ballot(((uint32_t)(uintptr_t)L.chunk & 127u) != 0 && L.live && nst != 0) == 0;
+    if (kShift && !lined) {
+      const uint64_t ca = (uint64_t)(uintptr_t)L.chunk;
+      run_lines(h, st, row_set<true, true>(nullptr, ca, nst, smax, img), ((uint32_t)ca >> 4) & 7u);
     } else {
-      // Cache policy per wave: CP (nt for the product kernels) when every
-      // row starts on a 128-B line; otherwise each 128-B stage straddles two
-      // lines and shares one with the row's next stage, and nt loads let that
-      // line leave L2 before the next stage asks for it (16-B-packed ragged
-      // blocks: 1.83x HBM bytes, 1.35x time), so such waves load with the
-      // default policy (profiles/r02_desc_cache_policy_ab.json).
-      const bool lined =
-          __ballot(((uint32_t)(uintptr_t)chunk & 127u) != 0 && live && nst != 0) == 0;
-      // Until the first row runs out (stage rmin), no row's stage index is
-      // clamped and the stage offset is wave-uniform: one 64-bit add per row
-      // with the offset in SGPRs instead of min + shift + add (16 VALU fewer
-      // per 128-B stage, ~2.5 % of the stage's VALU).
-      const uint32_t rmin = wave_min(nst ? nst : smax) - 1u;
-      // the image as an LDS pointer once: a generic pointer per DMA costs a
-      // null-check select (2 SALU) per row and stage
-      auto* limg = (__attribute__((address_space(3))) uint8_t*)img;
+      const RowSet rs = row_set<Src::kAbs>(base, L.off, nst, smax, img);
       auto run = [&](auto pol) __attribute__((always_inline)) {
         constexpr int P = decltype(pol)::value;
-        auto issue = [&](uint32_t stg) __attribute__((always_inline)) {
-          if (stg <= rmin) {                                   // wave-uniform
-            const uint64_t so = (uint64_t)stg << 7;
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-              __builtin_amdgcn_global_load_lds(rptr[r] + so, limg + r * 1024, 16, 0, P);
-          } else {
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-              __builtin_amdgcn_global_load_lds(rptr[r] + (min(stg, rlast[r]) << 7), limg + r * 1024,
-                                               16, 0, P);
-          }
-        };
-        issue(0);
-        for (uint32_t stg = 0; stg < smax; ++stg) {
-          // hipcc does not order ds_read after an LDS-DMA into the same bytes
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          uint4 w[2][4];
-          read_row(w);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads done before the refill
-          if (stg + 1 < smax) issue(stg + 1);
-          __builtin_amdgcn_sched_barrier(0);
-          if (stg < nst) {
-            h.block(st, w[0]);
-            h.block(st, w[1]);
-          }
-        }
+        if constexpr (NB == 2) run_stages2<P>(h, st, rs, L.live);
+        else run_stages<P>(h, st, rs);
       };
-      // kShift: whole lines.  Row r's line L is the 128-B line L of its chunk's
-      // line-aligned base; window k (chunk bytes [128k, 128k + 128)) is line k
-      // from piece s on, then line k + 1's first s pieces.  A lane reads line
-      // L rotated by s (piece q of the read = line piece (q + s) & 7), so
-      // window k's piece q is line k's read for q + s < 8, line k+1's after.
-      // Lines 0..smax (a row with s > 0 needs line nst; one with s = 0 is
-      // clamped to its own last stage).
-      auto run_lines = [&]() __attribute__((always_inline)) {
-        // rptr / rlast re-pointed at lines (their stage values are dead here)
-        const uint64_t ca = (uint64_t)(uintptr_t)chunk;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          uint32_t row = (uint32_t)r * 8u + (lane >> 3);
-          const uint32_t rn = (uint32_t)__shfl((int)nst, (int)row, 64);
-          if (rn == 0) row = mrow;
-          const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)ca, (int)row, 64);
-          const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(ca >> 32), (int)row, 64);
-          const uint32_t part = (lane & 7u) ^ ((row >> 1) & 7u);      // source swizzle (xpose)
-          rptr[r] = reinterpret_cast<const uint8_t*>(
-              (uintptr_t)((((uint64_t)hi << 32) | (lo & ~127u)) + part * 16u));
-          rlast[r] = (rn ? rn : smax) - 1u + ((lo & 127u) != 0u);
-        }
-        auto issue = [&](uint32_t L) __attribute__((always_inline)) {
-          if (L <= rmin) {                                     // wave-uniform, no row clamped
-            const uint64_t so = (uint64_t)L << 7;
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-              __builtin_amdgcn_global_load_lds(rptr[r] + so, limg + r * 1024, 16, 0, 0);
-          } else {
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-              __builtin_amdgcn_global_load_lds(rptr[r] + (min(L, rlast[r]) << 7), limg + r * 1024, 16,
-                                               0, 0);
-          }
-        };
-        const uint32_t sh = ((uint32_t)ca >> 4) & 7u;
-        auto read_rot = [&](uint4 (&R)[2][4]) __attribute__((always_inline)) {
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const u32x4 v = *reinterpret_cast<const u32x4*>(myrow + ((((q + sh) & 7u) ^ g) * 16));
-            R[q >> 2][q & 3] = make_uint4(v.x, v.y, v.z, v.w);
-          }
-        };
-        uint4 ra[2][4], rb[2][4];
-        issue(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        read_rot(ra);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        issue(1);
-        // window k: `cur` (line k) completed in place from `nxt` (line k + 1,
-        // read here; the next window's `cur`)
-        auto step = [&](uint32_t k, uint4 (&cur)[2][4], uint4 (&nxt)[2][4]) __attribute__((always_inline)) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          read_rot(nxt);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads done before the refill
-          if (k + 2 <= smax) issue(k + 2);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int q = 0; q < 8; ++q)
-            if ((uint32_t)q + sh >= 8u) cur[q >> 2][q & 3] = nxt[q >> 2][q & 3];
-          if (k < nst) {
-            h.block(st, cur[0]);
-            h.block(st, cur[1]);
-          }
-        };
-        for (uint32_t k = 0; k < smax; k += 2) {
-          step(k, ra, rb);
-          if (k + 1 < smax) step(k + 1, rb, ra);
-        }
-      };
-      if (kShift && !lined) run_lines();
-      else if (CP == 0 || !lined) run(std::integral_constant<int, 0>{});
+      if (CP == 0 || !lined) run(std::integral_constant<int, 0>{});
       else run(std::integral_constant<int, CP>{});
     }
   }
-  if (live) {
-    if (nfull & 1u) {
+  if (L.live) {
+    if (L.nfull & 1u) {
       uint4 w[4];
-      load_block(w, reinterpret_cast<const uint4*>(chunk + ((uint64_t)(nfull - 1) << 6)));
+      load_block(w, reinterpret_cast<const uint4*>(L.chunk + ((uint64_t)(L.nfull - 1) << 6)));
       h.block(st, w);
     }
-    h.finish(st, chunk + ((uint64_t)nfull << 6), len & 63u, len);
-    emit<Src>(h, out, c, st);
+    h.finish(st, L.chunk + ((uint64_t)L.nfull << 6), L.len & 63u, L.len);
+    emit<Src>(h, out, L.c, st);
   }
 }
 
@@ -1025,8 +1095,7 @@ __device__ __forceinline__ State fed_long_group(const uint8_t* __restrict__ base
 // (profiles/r03q/small_fed_*.json).  A group holding a chunk start that is
 // not 16-B aligned, or no chunk of two whole blocks, runs LANE's lane-direct
 // body on wave 0 instead.
-// kImplicit: chunk i at base + i * stride, `flen` bytes (the fixed-length
-// API's small batches).
+// kImplicit: the fixed-length API's small batches (chunk_source).
 constexpr uint32_t kFedMinBlocks = MD5HIP_FED_MIN_BLOCKS;
 
 template <bool kImplicit>
@@ -1036,26 +1105,19 @@ md5_desc_fed(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs
              uint64_t stride, uint32_t flen, uint4* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[2 * kFedTable];
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const DescArrays src{offs, lens, order};
-  const uint64_t first = (uint64_t)blockIdx.x * 64u;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t i = first + lane;
-  const bool live = i < n;
-  const uint64_t c = kImplicit ? (live ? i : first) : src.index(live ? i : first);
-  const uint64_t off = kImplicit ? c * stride : src.off(c);
-  const uint32_t len = live ? (kImplicit ? flen : src.len(c)) : 0u;
-  const uint32_t nfull = len >> 6;
-  const uint32_t bmax = wave_max(nfull);
-  const bool unaligned = __ballot(live && ((((uintptr_t)base + off) & 15u) != 0)) != 0;
+  const GroupLane L = group_lane(chunk_source<kImplicit>(offs, lens, order, stride, flen), base, n,
+                                 (uint64_t)blockIdx.x * 64u);
+  const uint32_t bmax = wave_max(L.nfull);
+  const bool unaligned = L.any_unaligned();
   if (bmax >= kFedMinBlocks && !unaligned) {     // wave-uniform, the same in both waves
-    fed_long_group(base, out, lds, wave == 1, nfull, bmax, off, len, c, live);
+    fed_long_group(base, out, lds, wave == 1, L.nfull, bmax, L.off, L.len, L.c, L.live);
     return;
   }
-  if (wave != 0 || !live) return;
+  if (wave != 0 || !L.live) return;
   Md5Hasher<true> h;
   typename Md5Hasher<true>::State st = h.init();
-  lane_range<Md5Hasher<true>, 8>(h, st, base + off, len);
-  h.store(out, c, st);
+  lane_range<Md5Hasher<true>, 8>(h, st, L.chunk, L.len);
+  h.store(out, L.c, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1069,9 +1131,9 @@ md5_desc_fed(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs
 // loaded unevenly: 1 MiB chains ran 2x their solo time sharing a SIMD and
 // SIMDs went idle from 54 % of the launch on (scripts/c3_trace_x.py, deleted in 4de68d0,
 // profiles/r02_c3_trace.json).  Here every SIMD takes the next-longest group
-// whenever its wave frees up.  ctr[0] hands out groups, ctr[1] counts waves
-// done; the last wave out resets both, so a counter serves the next launch
-// on its stream (md5_kernels.hip keeps one per device and stream).
+// whenever its wave frees up.  ctr[0] hands out groups, ctr[2] counts waves
+// done; the last wave out resets the counters, so they serve the next launch
+// on their stream (md5_kernels.hip keeps one set per device and stream).
 // ---------------------------------------------------------------------------
 // WPB waves per workgroup (one per SIMD at 4, two at 8), each with NB 8 KiB
 // LDS-DMA images; the workgroup asks for more than half the CU's LDS, so a
@@ -1080,8 +1142,8 @@ template <int WPB, int NB = 1>
 struct BalancedCfg {
   static constexpr uint32_t kWave = NB * 8192u;
   // the images start kImgPad bytes in: a DMA whose instruction offset
-  // carries the stage step (desc_xpose_group, NB = 2) takes M0 = image -
-  // up to 512 B
+  // carries the stage step (run_stages2's quads) takes M0 = image - up to
+  // 512 B
   static constexpr uint32_t kImgPad = 512u;
   static constexpr uint32_t kLds = WPB * kWave + kImgPad > 81920u ? WPB * kWave + kImgPad : 81920u + 16384u;
   static_assert(WPB * kWave + kImgPad <= 160u * 1024u, "LDS per CU");
@@ -1130,7 +1192,7 @@ __device__ __forceinline__ uint32_t balanced_body(const uint8_t* __restrict__ ba
 
 // the product's shape (profiles/r02_c3_balanced_ab.json,
 // r02_c3_wide_ab.json, r02_c3_cache_policy_ab.json): one wave per SIMD, two
-// 8 KiB images of 128-B stages (round 4, below), one queue, the DEFAULT cache policy for any
+// 8 KiB images of 128-B stages (run_stages2), one queue, the DEFAULT cache policy for any
 // group with a chunk off the 128-B line (nt only for line-aligned groups,
 // as every LDS-DMA loader here).  A C3 chunk
 // starts 16-B aligned, so each 128-B stage straddles two lines and shares one
@@ -1164,19 +1226,31 @@ md5_desc_balanced_t(const uint8_t* __restrict__ base, const uint64_t* __restrict
 // XDMA16: Crc32PermHasher's 16-copy tables (64 KiB) beside twelve waves' full
 // 8 KiB images filled by LDS-DMA (xdma_group, as the MD5 default): no VGPR
 // staging, no ds_write.  One 768-thread workgroup per CU (160 KiB LDS),
-// grid-stride over 64-chunk groups, wave-major (wave w of workgroup b starts
+// grid-stride over 64-row groups, wave-major (wave w of workgroup b starts
 // at group w * gridDim.x + b).
+// The frame: hasher H's tables at `lds`, this wave's image after them, and
+// group(h, first, img) for each of the wave's groups of `rows` rows.
+template <class H>
+constexpr uint32_t kXdma16Lds = H::kLdsBytes + 12 * 8192;
+
+template <class H, class Group>
+__device__ __forceinline__ void xdma16_frame(uint8_t* lds, uint64_t rows, Group group) {
+  H h;
+  h.setup(lds);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint8_t* img = lds + H::kLdsBytes + wave * 8192u;
+  const uint64_t ngroups = (rows + 63) / 64;
+  for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u)
+    group(h, gi * 64u, img);
+}
+
 __global__ void __launch_bounds__(768)
 crc32_fixed_xdma16(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uint64_t stride,
                    uint32_t* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[Crc32PermHasher::kLdsBytes + 12 * 8192];
-  Crc32PermHasher h;
-  h.setup(lds);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint8_t* img = lds + Crc32PermHasher::kLdsBytes + wave * 8192u;
-  const uint64_t ngroups = (n + 63) / 64;
-  for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u)
-    xdma_group(h, base, n, len, stride, gi * 64u, out, img);
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kXdma16Lds<Crc32PermHasher>];
+  xdma16_frame<Crc32PermHasher>(lds, n, [&](auto& h, uint64_t first, uint8_t* img) __attribute__((always_inline)) {
+    xdma_group(h, base, n, len, stride, first, out, img);
+  });
 }
 
 // Descriptor batches with XDMA16's layout: the descriptor loader's per-row
@@ -1185,14 +1259,10 @@ __global__ void __launch_bounds__(768)
 crc32_desc_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
                   const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order,
                   uint64_t n, uint32_t* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[Crc32PermHasher::kLdsBytes + 12 * 8192];
-  Crc32PermHasher h;
-  h.setup(lds);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint8_t* img = lds + Crc32PermHasher::kLdsBytes + wave * 8192u;
-  const uint64_t ngroups = (n + 63) / 64;
-  for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u)
-    desc_xpose_group<2>(h, base, DescArrays{offs, lens, order}, n, gi * 64u, out, img);
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kXdma16Lds<Crc32PermHasher>];
+  xdma16_frame<Crc32PermHasher>(lds, n, [&](auto& h, uint64_t first, uint8_t* img) __attribute__((always_inline)) {
+    desc_xpose_group<2>(h, base, DescArrays{offs, lens, order}, n, first, out, img);
+  });
 }
 
 // MD5 + CRC-32 in one pass (Md5Crc32Hasher, 32-B records) in XDMA16's frame:
@@ -1201,68 +1271,47 @@ crc32_desc_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__
 __global__ void __launch_bounds__(768)
 md5crc32_fixed_xdma16(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uint64_t stride,
                       Md5Crc32Record* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[Md5Crc32Hasher::kLdsBytes + 12 * 8192];
-  Md5Crc32Hasher h;
-  h.setup(lds);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint8_t* img = lds + Md5Crc32Hasher::kLdsBytes + wave * 8192u;
-  const uint64_t ngroups = (n + 63) / 64;
-  for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u)
-    xdma_group(h, base, n, len, stride, gi * 64u, out, img);
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kXdma16Lds<Md5Crc32Hasher>];
+  xdma16_frame<Md5Crc32Hasher>(lds, n, [&](auto& h, uint64_t first, uint8_t* img) __attribute__((always_inline)) {
+    xdma_group(h, base, n, len, stride, first, out, img);
+  });
 }
 
-// Fixed-length chunks as a descriptor source: chunk i at i * stride, flen
-// bytes (a base or stride off the 16-B grid, or a stride past xdma_group's
-// 32-bit offsets).
-struct FixedChunks {
-  uint64_t stride;
-  uint32_t flen;
-  static constexpr bool kPairXor = false;
-  static constexpr bool kAbs = false;
-  __device__ __forceinline__ uint64_t index(uint64_t i) const { return i; }
-  __device__ __forceinline__ uint64_t off(uint64_t c) const { return c * stride; }
-  __device__ __forceinline__ uint32_t len(uint64_t) const { return flen; }
-};
-
-// kImplicit: FixedChunks (offs, lens and order unused), else DescArrays.
 template <bool kImplicit>
 __global__ void __launch_bounds__(768)
 md5crc32_desc_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
                      const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order,
                      uint64_t n, uint64_t stride, uint32_t flen, Md5Crc32Record* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[Md5Crc32Hasher::kLdsBytes + 12 * 8192];
-  Md5Crc32Hasher h;
-  h.setup(lds);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint8_t* img = lds + Md5Crc32Hasher::kLdsBytes + wave * 8192u;
-  const uint64_t ngroups = (n + 63) / 64;
-  for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u) {
-    if constexpr (kImplicit)
-      desc_xpose_group<2, Md5Crc32Hasher, 0, FixedChunks>(h, base, FixedChunks{stride, flen}, n, gi * 64u,
-                                                         out, img);
-    else
-      desc_xpose_group<2>(h, base, DescArrays{offs, lens, order}, n, gi * 64u, out, img);
-  }
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kXdma16Lds<Md5Crc32Hasher>];
+  const auto src = chunk_source<kImplicit>(offs, lens, order, stride, flen);
+  using Src = std::remove_const_t<decltype(src)>;
+  xdma16_frame<Md5Crc32Hasher>(lds, n, [&](auto& h, uint64_t first, uint8_t* img) __attribute__((always_inline)) {
+    desc_xpose_group<2, Md5Crc32Hasher, 0, Src>(h, base, src, n, first, out, img);
+  });
+}
+
+// The fastcrc kernels' source from their arguments (offs == nullptr:
+// fixed-length chunks, k * stride, flen).
+__device__ __forceinline__ FastWindows fast_windows(const uint64_t* __restrict__ offs,
+                                                    const uint32_t* __restrict__ lens, uint64_t stride,
+                                                    uint32_t flen, uint32_t F) {
+  return {EitherChunks{DescArrays{offs, lens, nullptr}, FixedChunks{stride, flen}}, F};
 }
 
 // fastcrc (blk_io.c:408-424) through the same LDS-DMA loader: each 64-row
 // wave group is 32 chunks' head and tail windows (FastWindows), F bytes each,
 // so a wave-instruction still reads whole 128-B runs of 8 windows; lane pairs
-// XOR their CRCs.  offs == nullptr: fixed-length chunks (k * stride, flen).
+// XOR their CRCs.
 __global__ void __launch_bounds__(768)
 crc32_fast_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
                   const uint32_t* __restrict__ lens, uint64_t n, uint64_t stride, uint32_t flen,
                   uint32_t F, uint32_t* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[Crc32PermHasher::kLdsBytes + 12 * 8192];
-  Crc32PermHasher h;
-  h.setup(lds);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint8_t* img = lds + Crc32PermHasher::kLdsBytes + wave * 8192u;
-  const FastWindows src{offs, lens, stride, flen, F};
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kXdma16Lds<Crc32PermHasher>];
+  const FastWindows src = fast_windows(offs, lens, stride, flen, F);
   const uint64_t rows = 2 * n;
-  const uint64_t ngroups = (rows + 63) / 64;
-  for (uint64_t gi = (uint64_t)wave * gridDim.x + blockIdx.x; gi < ngroups; gi += (uint64_t)gridDim.x * 12u)
-    desc_xpose_group<2, Crc32PermHasher, 0, FastWindows>(h, base, src, rows, gi * 64u, out, img);
+  xdma16_frame<Crc32PermHasher>(lds, rows, [&](auto& h, uint64_t first, uint8_t* img) __attribute__((always_inline)) {
+    desc_xpose_group<2, Crc32PermHasher, 0, FastWindows>(h, base, src, rows, first, out, img);
+  });
 }
 
 // fastcrc with F = 64 or 128 (the netcache harness runs 128): every window
@@ -1283,39 +1332,30 @@ crc32_fast_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__
 // reaches L2 while the first half's fill is still pending there; loaded as
 // two runs of four (0..48, then 64..112), 15 % of second halves found their
 // line already evicted and fetched it again.
-__device__ __forceinline__ void fast_pipe_body(const uint8_t* __restrict__ base,
-                                               const uint64_t* __restrict__ offs,
-                                               const uint32_t* __restrict__ lens, uint64_t n,
-                                               uint64_t stride, uint32_t flen, uint32_t F,
-                                               uint32_t* __restrict__ out, uint8_t* lds) {
+__device__ __forceinline__ void fast_pipe_body(const uint8_t* __restrict__ base, const FastWindows& src,
+                                               uint64_t n, uint32_t* __restrict__ out, uint8_t* lds) {
   constexpr int D = 2;                                    // window groups in flight per wave
   Crc32PermHasher h;
   h.setup(lds);
-  const FastWindows src{offs, lens, stride, flen, F};
-  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t F = src.F;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint64_t rows = 2 * n;
   const uint64_t ngroups = (rows + 63) / 64;
   const uint64_t step = (uint64_t)gridDim.x * (blockDim.x >> 6);
   const uint32_t nb = F >> 6;                             // 1 or 2 blocks per window
   struct Win {
-    const uint8_t* p;
-    uint32_t len;
-    bool live;
+    GroupLane l;                                          // dead lanes read a live row
     bool pipe;                                            // wave-uniform
   };
   auto locate = [&](uint64_t gi) __attribute__((always_inline)) {
     Win w;
-    const uint64_t c = gi * 64u + lane;
-    w.live = c < rows;
-    w.len = w.live ? src.len(c) : 0u;
-    w.p = base + src.off(w.live ? c : gi * 64u);         // dead lanes read a live row
-    const bool simple = !w.live || (w.len == F && ((uintptr_t)w.p & 15u) == 0);
+    w.l = group_lane(src, base, rows, gi * 64u);
+    const bool simple = !w.l.live || (w.l.len == F && ((uintptr_t)w.l.chunk & 15u) == 0);
     w.pipe = __ballot(!simple) == 0;
     return w;
   };
   auto fetch = [&](const Win& w, uint4 (&W)[2][4]) __attribute__((always_inline)) {
-    const uint4* q = reinterpret_cast<const uint4*>(w.p);
+    const uint4* q = reinterpret_cast<const uint4*>(w.l.chunk);
     if (nb == 2) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {      // the barriers keep hipcc from sorting by offset
@@ -1333,11 +1373,11 @@ __device__ __forceinline__ void fast_pipe_body(const uint8_t* __restrict__ base,
     if (w.pipe) {
       h.block(st, W[0]);
       if (nb == 2) h.block(st, W[1]);
-      h.finish(st, w.p, 0u, F);
-    } else if (w.live) {
-      lane_range<Crc32PermHasher, 2>(h, st, w.p, w.len);
+      h.finish(st, w.l.chunk, 0u, F);
+    } else if (w.l.live) {
+      lane_range<Crc32PermHasher, 2>(h, st, w.l.chunk, w.l.len);
     }
-    if (w.live) emit<FastWindows>(h, out, gi * 64u + lane, st);
+    if (w.l.live) emit<FastWindows>(h, out, gi * 64u + (threadIdx.x & 63u), st);   // = w.l.c, not kept in flight
   };
   uint64_t g0 = (uint64_t)wave * gridDim.x + blockIdx.x;
   if (g0 >= ngroups) return;
@@ -1376,7 +1416,7 @@ crc32_fast_pipe(const uint8_t* __restrict__ base, const uint64_t* __restrict__ o
                 const uint32_t* __restrict__ lens, uint64_t n, uint64_t stride, uint32_t flen,
                 uint32_t F, uint32_t* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[Crc32PermHasher::kLdsBytes];
-  fast_pipe_body(base, offs, lens, n, stride, flen, F, out, lds);
+  fast_pipe_body(base, fast_windows(offs, lens, stride, flen, F), n, out, lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -1445,10 +1485,11 @@ crc32_split(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t wpb = blockDim.x >> 6;
+  const auto src = chunk_source<kImplicit>(offs, lens, order, stride, flen);
   for (uint64_t q = (uint64_t)blockIdx.x * wpb + wave; q < n; q += (uint64_t)gridDim.x * wpb) {
-    const uint64_t c = (!kImplicit && order) ? (uint64_t)order[q] : q;
-    const uint8_t* m = base + (kImplicit ? c * stride : offs[c]);
-    const uint32_t L = kImplicit ? flen : lens[c];
+    const uint64_t c = src.index(q);
+    const uint8_t* m = chunk_at<decltype(src)::kAbs>(base, src.off(c));
+    const uint32_t L = src.len(c);
     uint32_t crc;
     if (F && L > F)
       crc = split_crc_msg(h, m, F, lane) ^ split_crc_msg(h, m + (L - F), F, lane);
@@ -1464,7 +1505,7 @@ crc32_desc(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
            const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order, uint64_t n,
            uint64_t stride, uint32_t flen, uint32_t* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t tabs[Crc32Hasher::kLdsBytes];
-  desc_body<kImplicit, Crc32Hasher, 4>(base, offs, lens, order, n, stride, flen, out, tabs);
+  desc_body<Crc32Hasher, 4>(base, chunk_source<kImplicit>(offs, lens, order, stride, flen), n, out, tabs);
 }
 
 // ---------------------------------------------------------------------------
@@ -1494,6 +1535,46 @@ __device__ __forceinline__ void ctx_store(uint32_t* p, const CtxWords& c) {
 #pragma unroll
   for (int k = 0; k < 22; ++k) p[k] = c.w[k];
 }
+
+// What an update of `len` bytes does to a context whose low bit-count word is
+// bits0: t bytes are pending; append_only (md5.c:189-192): no block
+// completes; otherwise the first `pos` bytes complete the pending block and
+// nblk whole blocks follow them (md5.c:204-210).  Both waves of a fed pair
+// take their group's block counts from here, so they meet at every barrier.
+struct CtxSpan {
+  uint32_t t, pos, nblk;
+  bool append_only;
+};
+__device__ __forceinline__ CtxSpan ctx_span(uint32_t bits0, uint32_t len) {
+  CtxSpan s;
+  s.t = (bits0 >> 3) & 63u;
+  s.append_only = s.t && len < 64u - s.t;
+  s.pos = s.append_only ? 0u : (s.t ? 64u - s.t : 0u);
+  s.nblk = s.append_only ? 0u : (len - s.pos) >> 6;
+  return s;
+}
+
+// data[0 .. count) into the bytes from `at` on of a block held as 16
+// little-endian words (at + count <= 64).
+__device__ __forceinline__ void put_bytes(uint32_t (&w)[16], uint32_t at, const uint8_t* data,
+                                          uint32_t count) {
+  for (uint32_t k = 0; k < count; ++k) {
+    const uint32_t p2 = at + k;
+    const uint32_t b = data[k];
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if ((uint32_t)j == (p2 >> 2)) {
+        const uint32_t sh = 8u * (p2 & 3u);
+        w[j] = (w[j] & ~(0xFFu << sh)) | (b << sh);
+      }
+  }
+}
+
+// The first nb bytes of a little-endian word (nb <= 0: none, >= 4: all).
+__device__ __forceinline__ uint32_t tail_mask(int nb) {
+  return nb >= 4 ? 0xFFFFFFFFu : nb <= 0 ? 0u : ((1u << (8 * nb)) - 1u);
+}
+
 // The whole 64-B blocks of an update go through the descriptor loader
 // (desc_xpose_group: LDS-DMA 128-B stages of 8 contexts' data per
 // wave-instruction, per-lane trip counts), each lane starting from its own
@@ -1517,7 +1598,8 @@ struct LaneSpan {
 };
 
 // One wave per 64 contexts (one-wave workgroups, the loader's 8 KiB image);
-// 125 VGPRs hold it at 4 waves per SIMD, as md5_desc_xdma's clobber does.
+// its VGPRs (just under 128) hold it at 4 waves per SIMD, as md5_desc_xdma's
+// clobber does.
 // The body, per wave.  kFed: the whole blocks run as the
 // chain wave of a fed pair (md5_update_ctx_fed, bmax = the group's most
 // blocks); otherwise through the descriptor loader into `img` (8 KiB).
@@ -1538,45 +1620,25 @@ __device__ __forceinline__ void update_ctx_body(uint32_t* __restrict__ ctxs,
   const uint32_t lo = t0 + (len << 3);                 // md5.c:179-182
   c.w[5] += (lo < t0 ? 1u : 0u) + (len >> 29);
   c.w[4] = lo;
-  const uint32_t t = (t0 >> 3) & 63u;
+  const CtxSpan sp = ctx_span(t0, len);
+  const uint32_t t = sp.t, nblk = sp.nblk;
+  const bool append_only = sp.append_only;
   uint32_t in[16];
 #pragma unroll
   for (int j = 0; j < 16; ++j) in[j] = c.w[6 + j];
-  const bool append_only = t && len < 64u - t;         // md5.c:189-192: no block completes
   State st{c.w[0], c.w[1], c.w[2], c.w[3]};
-  uint32_t pos = 0;                                    // bytes of data consumed
+  uint32_t pos = sp.pos;                               // bytes of data consumed
   uint32_t last[16];                                   // the last block compressed
   bool any = false;
   if (append_only) {
-    for (uint32_t k = 0; k < len; ++k) {
-      const uint32_t p2 = t + k;
-      const uint32_t b = data[k];
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        if ((uint32_t)j == (p2 >> 2)) {
-          const uint32_t sh = 8u * (p2 & 3u);
-          in[j] = (in[j] & ~(0xFFu << sh)) | (b << sh);
-        }
-    }
+    put_bytes(in, t, data, len);
   } else if (t) {                                      // md5.c:194-199: complete the pending block
-    const uint32_t need = 64u - t;
 #pragma unroll
     for (int j = 0; j < 16; ++j) last[j] = in[j];
-    for (uint32_t k = 0; k < need; ++k) {
-      const uint32_t p2 = t + k;
-      const uint32_t b = data[k];
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        if ((uint32_t)j == (p2 >> 2)) {
-          const uint32_t sh = 8u * (p2 & 3u);
-          last[j] = (last[j] & ~(0xFFu << sh)) | (b << sh);
-        }
-    }
+    put_bytes(last, t, data, 64u - t);
     compress(st, [&](int q) __attribute__((always_inline)) { return last[q]; });
-    pos = need;
     any = true;
   }
-  const uint32_t nblk = append_only ? 0u : (len - pos) >> 6;   // md5.c:204-210
   if constexpr (kFed) {
     st = fed_long_group<false, true>(nullptr, nullptr, img, false, nblk, bmax,
                                      (uint64_t)(uintptr_t)(data + pos), nblk << 6, 0, live, st);
@@ -1614,8 +1676,7 @@ __device__ __forceinline__ void update_ctx_body(uint32_t* __restrict__ ctxs,
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const uint32_t keep = any ? last[j] : in[j];
-    const int nb = (int)r - 4 * j;                     // tail bytes in word j
-    const uint32_t m = nb >= 4 ? 0xFFFFFFFFu : nb <= 0 ? 0u : ((1u << (8 * nb)) - 1u);
+    const uint32_t m = tail_mask((int)r - 4 * j);      // tail bytes in word j
     c.w[6 + j] = (tw[j] & m) | (keep & ~m);
   }
   c.w[0] = st.a; c.w[1] = st.b; c.w[2] = st.c; c.w[3] = st.d;
@@ -1644,10 +1705,8 @@ md5_update_ctx_fed(uint32_t* __restrict__ ctxs, const uint64_t* __restrict__ ptr
   const bool live = i < n;
   const uint32_t len = live ? lens[i] : 0u;
   const uint8_t* data = reinterpret_cast<const uint8_t*>(live ? ptrs[i] : 0ull);
-  const uint32_t t = (ctxs[22 * (live ? i : first) + 4] >> 3) & 63u;   // pending bytes
-  const bool append_only = t && len < 64u - t;
-  const uint32_t pos = append_only ? 0u : (t ? 64u - t : 0u);
-  const uint32_t nblk = append_only ? 0u : (len - pos) >> 6;
+  const CtxSpan sp = ctx_span(ctxs[22 * (live ? i : first) + 4], len);
+  const uint32_t pos = sp.pos, nblk = sp.nblk;
   const uint32_t bmax = wave_max(nblk);
   const bool unaligned = __ballot(nblk && ((((uintptr_t)data + pos) & 15u) != 0)) != 0;
   if (bmax < kFedMinBlocks || unaligned) {     // wave-uniform, the same in both waves
@@ -1673,9 +1732,7 @@ md5_final_ctx(uint32_t* __restrict__ ctxs, uint64_t n, uint4* __restrict__ diges
   uint32_t w[16];
 #pragma unroll
   for (int j = 0; j < 16; ++j) {                       // in[0..count), 0x80, zeros (md5.c:233-254)
-    const int nb = (int)count - 4 * j;
-    const uint32_t m = nb >= 4 ? 0xFFFFFFFFu : nb <= 0 ? 0u : ((1u << (8 * nb)) - 1u);
-    w[j] = c.w[6 + j] & m;
+    w[j] = c.w[6 + j] & tail_mask((int)count - 4 * j);
     if ((uint32_t)j == (count >> 2)) w[j] |= 0x80u << (8u * (count & 3u));
   }
   State st{c.w[0], c.w[1], c.w[2], c.w[3]};

@@ -45,6 +45,7 @@ KERNELS = {
     "crc32_fast_xdma16": dict(src="windows", nb=1, shift=False),
     "md5crc32_desc_xdma16<implicit>": dict(src="fixed", nb=1, shift=False),
 }
+# the three loaders desc_xpose_group chooses from: run_stages, run_stages2, run_lines
 STAGE_PATHS = ("run", "run2", "run_lines")
 
 
@@ -99,7 +100,7 @@ def _group(a, L, live, k):
     rlast = rows - 1
     rmin = int(rows.min()) - 1
     lined = not bool((lv & (nst != 0) & ((a & 127) != 0)).any())
-    clamp = smax - 1 > rmin                        # issue()'s else branch is taken
+    clamp = smax - 1 > rmin                        # the loaders' clamped issue branch is taken
     standin = np.flatnonzero(nst == 0)
     g.update(mrow=mrow, rlast=rlast, rmin=rmin, lined=lined, clamp=clamp, standin=standin)
     f.add("lined" if lined else "unlined")

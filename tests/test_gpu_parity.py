@@ -153,7 +153,7 @@ def test_desc_long_and_short_waves(cuda, dv):
 
 
 def test_balanced_guard_free_stage_edges(cuda):
-    """BALANCED's guard-free stages (md5_kernels.h, desc_xpose_group NB = 2:
+    """BALANCED's guard-free stages (md5_kernels.h, run_stages2's quads:
     stages every live lane holds whole and no row clamps, four per loop test)
     hand over to the guarded stage at every boundary: 64-chunk groups of one
     length with 1..21 whole 128-B stages and each of 0 / 64 / 100 B more; the
