@@ -22,13 +22,9 @@ checked against the oracle).
                     only their windows) against the round-5 library before
                     that change (build/abr05/old, via LD_LIBRARY_PATH) and the
                     calling thread
-  --matrix watch    VERDICT r04 item 3: the blocked caller's watcher policy
-                    (MD5HIP_WATCH spin / tail / block, md5_submit.c
-                    watch_launch) at 8 / 64 / 256 callers of 64 x 16 KiB from
-                    registered pages, batcher and pool, interleaved rounds
 
 Writes one JSON file (--out) with every run; prints each run as it ends.
-usage: asio_scale.py --matrix threads|chunk [--secs 3] [--out FILE]"""
+usage: asio_scale.py --matrix threads|chunk|bigchunk|fastcrc [--secs 3] [--out FILE]"""
 import argparse
 import json
 import os
@@ -61,9 +57,7 @@ def run(target, threads, blocks, L, secs, mode="pageable", timeout=150, env=None
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrix", choices=["threads", "chunk", "bigchunk", "watch", "fastcrc"], required=True)
-    ap.add_argument("--rounds", type=int, default=2)
-    ap.add_argument("--policies", default="spin,tail,block", help="--matrix watch: MD5HIP_WATCH values")
+    ap.add_argument("--matrix", choices=["threads", "chunk", "bigchunk", "fastcrc"], required=True)
     ap.add_argument("--slice-mib", type=int, default=0, help="batcher slice (0 = the library default)")
     ap.add_argument("--secs", type=float, default=3.0)
     ap.add_argument("--sizes-kib", default="16,128,1024", help="--matrix chunk: block sizes in KiB")
@@ -75,13 +69,6 @@ def main():
             for target in ("batcher", "pool"):
                 for T in (8, 64, 256):
                     runs.append(run(target, T, 64, 16384, a.secs, mode))
-    elif a.matrix == "watch":
-        for r in range(a.rounds):
-            for target in ("batcher", "pool"):
-                for T in (8, 64, 256):
-                    for pol in a.policies.split(","):
-                        runs.append(run(target, T, 64, 16384, a.secs, "registered",
-                                        env={"MD5HIP_WATCH": pol}, tag={"watch": pol, "round": r}))
     elif a.matrix == "fastcrc":
         old = os.path.join(REPO, "build", "abr05", "old")
         for F in (128, 0):

@@ -46,6 +46,24 @@
  * their events say.  No digest of a failed launch is delivered.  The pool
  * (md5_pool.c) routes around a failed batcher; what the call site does with
  * -EIO / -ENODEV is INTEGRATION.md §2j.
+ *
+ * The parts, in the file's order:
+ *   registered host ranges   the table behind zero-copy input; the device guard
+ *   slots and tickets        the structures; descriptors and plan (slot_prepare);
+ *                            a launch as bytes in, kernel, digests out
+ *                            (slot_enqueue); retire, failure, the launch
+ *                            decision (slot_try_launch); the open slot and
+ *                            claiming a free one
+ *   progress thread          retire what finished, linger or sleep, prepare
+ *                            the open slot ahead, chain it, poll interval
+ *   blocked callers          the watcher of a launch, wait_ticket
+ *   create / destroy / settings
+ *   submission               reserve (descriptors, histogram, zero-copy
+ *                            tables), the engines submit and fixed_submit,
+ *                            wait / poll / flush
+ *   entries                  the C ABI's submit calls; the pool's; verify
+ * The ticket table is md5_tickets.h, the host chunk sources (segments,
+ * copies, the threaded gather) md5_source.h: both included here alone.
  */
 #include <errno.h>
 #include <pthread.h>
@@ -60,6 +78,7 @@
 #include "../../include/md5hip.h"
 #include "md5_internal.h"
 #include "md5_tickets.h"
+#include "md5_source.h"
 
 /* ------------------------------------------------------------------------
  * Registered host ranges (zero-copy input).  netcache allocates its cache
@@ -266,7 +285,6 @@ struct slot {
     int inject;
 };
 enum { WATCH_NONE = 0, WATCH_ACTIVE, WATCH_GAVE_UP };
-enum watch_policy { WATCH_POLICY_SPIN = 0, WATCH_POLICY_TAIL = 1, WATCH_POLICY_BLOCK = 2 };
 
 struct md5hip_batcher {
     int device;
@@ -297,7 +315,6 @@ struct md5hip_batcher {
     int chain;                /* chain the open slot behind the running launch: 0 off, 1 on, 2 (default) on + BALANCED tails overlap */
     hipEvent_t after_ev;     /* recorded on a producer's stream (md5_batch_submit_device_on) */
     int failed;               /* 0, or -ENODEV once the device failed (sticky; read lock-free by the pool) */
-    int watch_policy;         /* enum watch_policy (watch_launch), MD5HIP_WATCH at create */
     uint64_t inject_at;       /* md5hip_batcher_inject_fault: launch number that faults, 0 = none */
 };
 
@@ -339,8 +356,9 @@ static void wait_cv_us(md5hip_batcher *b, pthread_cond_t *cv, uint64_t us)
 static void wait_work_us(md5hip_batcher *b, uint64_t us) { wait_cv_us(b, &b->work_cv, us); }
 
 /* One segment per (ticket, slot): a submission fills a slot until it is full
- * before it moves on, so its chunks in one slot are one contiguous run. */
-static int seg_push(struct slot *sl, struct seg sg)
+ * before it moves on, so its chunks in one slot are one contiguous run.  The
+ * slot holds a reference on the ticket from here until it retires (mu held). */
+static int seg_push(md5hip_batcher *b, struct slot *sl, struct seg sg)
 {
     if (sl->nsegs == sl->capsegs) {
         const uint32_t nc = sl->capsegs ? 2 * sl->capsegs : 64;
@@ -351,7 +369,17 @@ static int seg_push(struct slot *sl, struct seg sg)
     }
     sl->segs[sl->nsegs++] = sg;
     sl->tickets_in++;
+    tk_ring_ref(&b->tk, sg.ticket);
     return 0;
+}
+
+/* Weight w (len + 64 per chunk) more in slot `sl` and in the batcher's load,
+ * which the pool's router reads without the lock (mu held).  A retiring slot
+ * takes its whole share out again: w = -sl->load, modulo 2^64. */
+static void load_add(md5hip_batcher *b, struct slot *sl, uint64_t w)
+{
+    sl->load += w;
+    __atomic_store_n(&b->load_bytes, b->load_bytes + w, __ATOMIC_RELAXED);
 }
 
 static int seg_has(const struct slot *sl, uint64_t t)
@@ -386,19 +414,24 @@ static int stable_order(struct slot *sl, uint64_t n)
     return e == -ENOSPC || e == -EINVAL ? 1 : e;
 }
 
-static int slot_prepare(md5hip_batcher *b, struct slot *sl)
+/* The descriptor entries not yet on the device, [copied_n, n), go there on
+ * the slot's stream (mu held, n > copied_n). */
+static int desc_copy(struct slot *sl)
 {
-    (void)b;
+    const uint64_t c0 = sl->copied_n, cn = sl->n - c0;
+    if (hipMemcpyAsync(sl->d_off + c0, sl->h_off + c0, 8 * cn, hipMemcpyHostToDevice, sl->stream) ||
+        hipMemcpyAsync(sl->d_len + c0, sl->h_len + c0, 4 * cn, hipMemcpyHostToDevice, sl->stream))
+        return -EIO;
+    sl->copied_n = sl->n;
+    return 0;
+}
+
+static int slot_prepare(struct slot *sl)
+{
     const uint64_t n = sl->n;
     if (sl->planned_n == n) return 0;
     sl->desc_direct = n <= DESC_DIRECT_MAX;
-    if (!sl->desc_direct && n > sl->copied_n) {
-        const uint64_t c0 = sl->copied_n;
-        if (hipMemcpyAsync(sl->d_off + c0, sl->h_off + c0, 8 * (n - c0), hipMemcpyHostToDevice, sl->stream) ||
-            hipMemcpyAsync(sl->d_len + c0, sl->h_len + c0, 4 * (n - c0), hipMemcpyHostToDevice, sl->stream))
-            return -EIO;
-        sl->copied_n = n;
-    }
+    if (!sl->desc_direct && n > sl->copied_n && desc_copy(sl)) return -EIO;
     int dvar, e = 0;
     if (!sl->unsorted) {
         dvar = sl->hovf ? md5hip_plan_desc(sl->h_len, n, sl->h_ord)
@@ -436,62 +469,56 @@ static int slot_prepare(md5hip_batcher *b, struct slot *sl)
     return 0;
 }
 
-/* Enqueue slot `sl` (mu held, writers == 0): bytes in, kernel, digests out. */
-static int slot_enqueue(md5hip_batcher *b, struct slot *sl)
+/* Bytes in for a staged or zero-copy slot: one H2D copy of the pinned
+ * staging, or the registered pages by the gather kernel or by DMA per run. */
+static int enqueue_bytes(md5hip_batcher *b, struct slot *sl)
 {
-    int rc = 0;
-    const uint64_t n = sl->n;
-    /* one submission whose digests stay on the device and fill the slot in
-     * order: the kernel writes them in place (no scatter launch) */
-    const struct seg *g0 = sl->nsegs == 1 ? &sl->segs[0] : NULL;
-    unsigned char *dst = sl->d_dig;
-    if (g0 && g0->on_device && g0->first == 0 && g0->count == n && ((uintptr_t)g0->user & 15u) == 0) {
-        dst = g0->user;
-        sl->direct = 1;
+    if (sl->mode == MODE_STAGED && sl->used) {
+        if (hipMemcpyAsync(sl->d_data, sl->h_data, sl->used, hipMemcpyHostToDevice, sl->stream))
+            return -EIO;
+    } else if (sl->mode == MODE_ZEROCOPY && sl->nseg) {
+        int mode = b->gather;
+        if (mode == MD5HIP_GATHER_AUTO)
+            /* measured: per-copy DMA beats the PCIe-reading
+             * gather kernel once copies average more than ~192 KiB */
+            mode = sl->ndma * (256u << 10) <= sl->used ? MD5HIP_GATHER_DMA : MD5HIP_GATHER_DEVICE;
+        if (mode == MD5HIP_GATHER_DEVICE) {
+            if (hipMemcpyAsync(sl->d_seg, sl->h_seg, sizeof(struct md5hip_seg) * sl->nseg,
+                               hipMemcpyHostToDevice, sl->stream))
+                return -EIO;
+            return md5hip_gather_launch(sl->d_seg, sl->nseg, sl->d_data, sl->stream);
+        }
+        /* one async copy per run (hipMemcpyBatchAsync is newer than the
+         * HIP runtime torch ships, which this library shares) */
+        for (uint64_t q = 0; q < sl->ndma; q++)
+            if (hipMemcpyAsync(sl->b_dst[q], sl->b_src[q], sl->b_len[q], hipMemcpyHostToDevice,
+                               sl->stream) != hipSuccess)
+                return -EIO;
     }
+    return 0;
+}
+
+/* The hash kernel, digests to `dst`, and `kdone` behind it. */
+static int enqueue_kernel(struct slot *sl, unsigned char *dst)
+{
+    int rc;
+    const uint64_t n = sl->n;
+    /* a chained launch: bytes in and plan made beside the running launch,
+     * the hash kernel after it.  Never a FIXED slot: chain_ev is set on the
+     * open slot only (chain_open), and a FIXED slot is never b->open */
+    if (sl->chain_ev && !sl->chain_overlap && hipStreamWaitEvent(sl->stream, sl->chain_ev, 0) != hipSuccess)
+        return -EIO;
     if (sl->mode == MODE_FIXED) {
         /* host_fixed: the bytes are on their way already (its copy was
          * enqueued on this stream outside b->mu); device_fixed: they are
          * read where the caller keeps them */
         const void *src = sl->fx_dev ? (const void *)sl->fx_src : (const void *)sl->d_data;
-        if (sl->chain_ev && hipStreamWaitEvent(sl->stream, sl->chain_ev, 0) != hipSuccess) return -EIO;
         rc = sl->kind == MD5HIP_DIGEST_CRC32
                  ? crc32hip_fixed(src, n, sl->fx_len, sl->fx_stride, sl->fastcrc, (uint32_t *)dst, sl->stream)
              : sl->kind == MD5HIP_DIGEST_MD5_CRC32
                  ? md5crc32hip_fixed(src, n, sl->fx_len, sl->fx_stride, (struct md5hip_md5crc32 *)dst, sl->stream)
                  : md5hip_digest_fixed(src, n, sl->fx_len, sl->fx_stride, dst, sl->stream);
-        if (rc) return rc;
-        if (hipEventRecord(sl->kdone, sl->stream)) return -EIO;
     } else {
-        if ((rc = slot_prepare(b, sl))) return rc;
-        const int dvar = sl->plan_var;
-        if (sl->mode == MODE_STAGED && sl->used) {
-            if (hipMemcpyAsync(sl->d_data, sl->h_data, sl->used, hipMemcpyHostToDevice, sl->stream))
-                return -EIO;
-        } else if (sl->mode == MODE_ZEROCOPY && sl->nseg) {
-            int mode = b->gather;
-            if (mode == MD5HIP_GATHER_AUTO)
-                /* measured: per-copy DMA beats the PCIe-reading
-                 * gather kernel once copies average more than ~192 KiB */
-                mode = sl->ndma * (256u << 10) <= sl->used ? MD5HIP_GATHER_DMA : MD5HIP_GATHER_DEVICE;
-            if (mode == MD5HIP_GATHER_DEVICE) {
-                if (hipMemcpyAsync(sl->d_seg, sl->h_seg, sizeof(struct md5hip_seg) * sl->nseg,
-                                   hipMemcpyHostToDevice, sl->stream))
-                    return -EIO;
-                if ((rc = md5hip_gather_launch(sl->d_seg, sl->nseg, sl->d_data, sl->stream))) return rc;
-            } else {
-                /* one async copy per run (hipMemcpyBatchAsync is newer than the
-                 * HIP runtime torch ships, which this library shares) */
-                for (uint64_t q = 0; q < sl->ndma; q++)
-                    if (hipMemcpyAsync(sl->b_dst[q], sl->b_src[q], sl->b_len[q], hipMemcpyHostToDevice,
-                                       sl->stream) != hipSuccess)
-                        return -EIO;
-            }
-        }
-        /* a chained launch: bytes in and plan made beside the running
-         * launch, the hash kernel after it */
-        if (sl->chain_ev && !sl->chain_overlap && hipStreamWaitEvent(sl->stream, sl->chain_ev, 0) != hipSuccess)
-            return -EIO;
         const uint32_t *ord = sl->use_order ? sl->d_ord : NULL;
         const uint64_t *doff = sl->desc_direct ? sl->dh_off : sl->d_off;
         const uint32_t *dlen = sl->desc_direct ? sl->dh_len : sl->d_len;
@@ -504,14 +531,20 @@ static int slot_enqueue(md5hip_batcher *b, struct slot *sl)
              : sl->kind == MD5HIP_DIGEST_MD5_CRC32      /* one frame for every batch: the plan's order only */
                  ? md5crc32hip_desc(sl->d_data, doff, dlen, ord, n, (struct md5hip_md5crc32 *)dst, sl->stream)
                  : md5hip_digest_desc_variant(sl->d_data, doff, dlen, ord, n,
-                                              dst, sl->stream, dvar);
-        if (rc) return rc;
-        if (hipEventRecord(sl->kdone, sl->stream)) return -EIO;
+                                              dst, sl->stream, sl->plan_var);
     }
-    /* digests out: one D2H for the host segments, one scatter for the device
-     * ones.  The scatter kernel runs one workgroup per entry, so a long
-     * segment is cut into pieces of DSC_PIECE bytes as the table has room
-     * (6 tickets of 79 K digests as 6 entries took 145 us) */
+    if (rc) return rc;
+    return hipEventRecord(sl->kdone, sl->stream) ? -EIO : 0;
+}
+
+/* Digests out: one D2H for the host segments, one scatter for the device
+ * ones, then `done`.  The scatter kernel runs one workgroup per entry, so a
+ * long segment is cut into pieces of DSC_PIECE bytes as the table has room
+ * (6 tickets of 79 K digests as 6 entries took 145 us) */
+static int enqueue_digests(md5hip_batcher *b, struct slot *sl)
+{
+    int rc;
+    const uint64_t n = sl->n;
     enum { DSC_PIECE = 64 << 10 };
     int any_host = 0;
     sl->ndsc = 0;
@@ -544,8 +577,25 @@ static int slot_enqueue(md5hip_batcher *b, struct slot *sl)
     if (any_host &&
         hipMemcpyAsync(sl->h_dig, sl->d_dig, (size_t)sl->dsz * n, hipMemcpyDeviceToHost, sl->stream))
         return -EIO;
-    if (hipEventRecord(sl->done, sl->stream)) return -EIO;
-    return 0;
+    return hipEventRecord(sl->done, sl->stream) ? -EIO : 0;
+}
+
+/* Enqueue slot `sl` (mu held, writers == 0): bytes in, kernel, digests out. */
+static int slot_enqueue(md5hip_batcher *b, struct slot *sl)
+{
+    int rc;
+    /* one submission whose digests stay on the device and fill the slot in
+     * order: the kernel writes them in place (no scatter launch) */
+    const struct seg *g0 = sl->nsegs == 1 ? &sl->segs[0] : NULL;
+    unsigned char *dst = sl->d_dig;
+    if (g0 && g0->on_device && g0->first == 0 && g0->count == sl->n && ((uintptr_t)g0->user & 15u) == 0) {
+        dst = g0->user;
+        sl->direct = 1;
+    }
+    /* a FIXED slot has no descriptors, and its bytes are in (enqueue_kernel) */
+    if (sl->mode != MODE_FIXED && ((rc = slot_prepare(sl)) || (rc = enqueue_bytes(b, sl)))) return rc;
+    if ((rc = enqueue_kernel(sl, dst))) return rc;
+    return enqueue_digests(b, sl);
 }
 
 static void slot_reset(struct slot *sl)
@@ -582,8 +632,7 @@ static void slot_retire(md5hip_batcher *b, struct slot *sl, int err)
             memcpy(g->user, sl->h_dig + (size_t)sl->dsz * g->first, (size_t)sl->dsz * g->count);
         tk_ring_put(&b->tk, g->ticket, err);
     }
-    __atomic_store_n(&b->load_bytes, b->load_bytes - sl->load, __ATOMIC_RELAXED);
-    sl->load = 0;
+    load_add(b, sl, -sl->load);
     if (sl->state == SLOT_INFLIGHT) {
         b->inflight--;
         /* a chained launch's start is estimated (chain_at): one that retires
@@ -596,7 +645,14 @@ static void slot_retire(md5hip_batcher *b, struct slot *sl, int err)
     }
     slot_reset(sl);
     if (sl->nwait) pthread_cond_broadcast(&sl->cv);   /* its waiters only */
-    pthread_cond_broadcast(&b->done_cv);              /* slot_take / drain / destroy */
+    pthread_cond_broadcast(&b->done_cv);              /* slot_wait / drain / destroy */
+}
+
+/* The OPEN slot new chunks go to, or NULL; `sl` is it no longer (mu held). */
+static struct slot *open_slot(const md5hip_batcher *b) { return b->open >= 0 ? &b->s[b->open] : NULL; }
+static void unopen(md5hip_batcher *b, const struct slot *sl)
+{
+    if (b->open == (int)(sl - b->s)) b->open = -1;
 }
 
 /* Is the device behind this HIP status gone (a fault, a lost or reset
@@ -627,7 +683,7 @@ static void batcher_fail(md5hip_batcher *b)
     for (uint32_t k = 0; k < b->nslots; k++) {
         struct slot *sl = &b->s[k];
         if (sl->state != SLOT_OPEN) continue;
-        if (b->open == (int)k) b->open = -1;
+        unopen(b, sl);
         sl->full = 1;
         if (!sl->err) sl->err = -ENODEV;
         if (!sl->writers) slot_retire(b, sl, sl->err);
@@ -664,7 +720,7 @@ static void slot_try_launch(md5hip_batcher *b, struct slot *sl)
      * nothing), the last slot coalesces whoever comes while they run */
     if (sl->urgent && b->inflight + 1 < b->nslots) sl->flush = 1;
     if (sl->n == 0) {                 /* nothing reserved (all chunks failed) */
-        if (b->open == (int)(sl - b->s)) b->open = -1;
+        unopen(b, sl);
         slot_retire(b, sl, sl->err);
         return;
     }
@@ -673,7 +729,7 @@ static void slot_try_launch(md5hip_batcher *b, struct slot *sl)
         pthread_cond_broadcast(&b->work_cv);        /* the progress thread times the linger */
         return;
     }
-    if (b->open == (int)(sl - b->s)) b->open = -1;
+    unopen(b, sl);
     const int rc = sl->err ? sl->err : b->failed ? b->failed : slot_enqueue(b, sl);
     if (rc) {
         /* an enqueue (here, or a descriptor copy or ordering made earlier:
@@ -716,30 +772,58 @@ static void slot_wait(md5hip_batcher *b)
     b->slot_waiters--;
 }
 
-/* A FREE slot made OPEN in `mode` for digests of `kind` (mu held; waits
- * for one to retire). */
+/* The open slot, looked at again / flushed (no linger, no inflight target) /
+ * closed: full, no longer b->open, launched once its writers are done
+ * (mu held; nothing when no slot is open). */
+static void try_open(md5hip_batcher *b)
+{
+    struct slot *o = open_slot(b);
+    if (o) slot_try_launch(b, o);
+}
+
+static void flush_open(md5hip_batcher *b)
+{
+    struct slot *o = open_slot(b);
+    if (!o) return;
+    o->flush = 1;
+    slot_try_launch(b, o);
+}
+
+static void close_open(md5hip_batcher *b)
+{
+    struct slot *o = open_slot(b);
+    if (!o) return;
+    o->full = 1;
+    b->open = -1;
+    slot_try_launch(b, o);
+}
+
+/* A FREE slot made OPEN in `mode` for digests of `kind`, or NULL (mu held). */
+static struct slot *slot_claim(md5hip_batcher *b, int mode, int kind, uint32_t fastcrc)
+{
+    for (uint32_t k = 0; k < b->nslots; k++) {
+        struct slot *sl = &b->s[k];
+        if (sl->state != SLOT_FREE) continue;
+        slot_reset(sl);
+        sl->state = SLOT_OPEN;
+        sl->mode = mode;
+        sl->kind = (uint32_t)kind;
+        sl->fastcrc = fastcrc;
+        sl->dsz = md5hip_digest_size(kind);
+        return sl;
+    }
+    return NULL;
+}
+
+/* A slot of the caller's own, not b->open (mu held; waits for one to retire). */
 static struct slot *slot_take(md5hip_batcher *b, int mode, int kind, uint32_t fastcrc)
 {
-    for (;;) {
-        for (uint32_t k = 0; k < b->nslots; k++) {
-            struct slot *sl = &b->s[k];
-            if (sl->state != SLOT_FREE) continue;
-            slot_reset(sl);
-            sl->state = SLOT_OPEN;
-            sl->mode = mode;
-            sl->kind = (uint32_t)kind;
-            sl->fastcrc = fastcrc;
-            sl->dsz = md5hip_digest_size(kind);
-            return sl;
-        }
-        /* all busy: make sure the open slot can go, then wait for a retire */
-        if (b->open >= 0) {
-            struct slot *o = &b->s[b->open];
-            o->full = 1;
-            slot_try_launch(b, o);
-        }
+    struct slot *sl;
+    while (!(sl = slot_claim(b, mode, kind, fastcrc))) {
+        close_open(b);                /* all busy: make sure the open slot can go */
         slot_wait(b);
     }
+    return sl;
 }
 
 /* The OPEN slot that accepts chunks of `mode` and digest `kind` (mu held). */
@@ -750,37 +834,127 @@ static struct slot *slot_take(md5hip_batcher *b, int mode, int kind, uint32_t fa
 static struct slot *slot_open(md5hip_batcher *b, int mode, int kind, uint32_t fastcrc)
 {
     for (;;) {
-        if (b->open >= 0) {
-            struct slot *o = &b->s[b->open];
+        struct slot *o = open_slot(b);
+        if (o) {
             const int compatible = (o->mode == mode || mode == MODE_NONE || o->mode == MODE_NONE) &&
                                    o->kind == (uint32_t)kind && o->fastcrc == fastcrc;
             if (!o->full && compatible && o->nsegs < b->segcap) {
                 if (o->mode == MODE_NONE) o->mode = mode;
                 return o;
             }
-            o->full = 1;                 /* closes: launched once its writers are done */
-            b->open = -1;
-            slot_try_launch(b, o);
+            close_open(b);
         }
-        for (uint32_t k = 0; k < b->nslots; k++) {
-            struct slot *sl = &b->s[k];
-            if (sl->state != SLOT_FREE) continue;
-            slot_reset(sl);
-            sl->state = SLOT_OPEN;
-            sl->mode = mode;
-            sl->kind = (uint32_t)kind;
-            sl->fastcrc = fastcrc;
-            sl->dsz = md5hip_digest_size(kind);
-            b->open = (int)k;
-            return sl;
+        if ((o = slot_claim(b, mode, kind, fastcrc))) {
+            b->open = (int)(o - b->s);
+            return o;
         }
         slot_wait(b);                                 /* all busy: wait for a retire */
     }
 }
 
+/* The slot the next chunks of a submission go to (mu held): one of its own
+ * for MODE_FIXED (straight from the caller's buffer; the open slot keeps
+ * coalescing other work), else the open slot.  NULL once the device has
+ * failed -- before, or while this waited for a slot: the empty slot it was
+ * given then retires. */
+static struct slot *slot_for(md5hip_batcher *b, int mode, int kind, uint32_t fastcrc)
+{
+    if (b->failed) return NULL;
+    struct slot *sl = (mode == MODE_FIXED ? slot_take : slot_open)(b, mode, kind, fastcrc);
+    if (!b->failed) return sl;
+    slot_try_launch(b, sl);
+    return NULL;
+}
+
 /* ------------------------------------------------------------------------
  * Progress thread: retire finished slots, launch coalesced work.
  * ------------------------------------------------------------------------ */
+/* Retire every in-flight slot whose launch has finished; were there any? */
+static int retire_finished(md5hip_batcher *b)
+{
+    int any = 0;
+    for (uint32_t k = 0; k < b->nslots; k++) {
+        struct slot *sl = &b->s[k];
+        if (sl->state != SLOT_INFLIGHT) continue;
+        const hipError_t e = launch_status(sl->done, sl->inject);
+        if (e == hipErrorNotReady) continue;
+        slot_complete(b, sl, e);
+        any = 1;
+    }
+    return any;
+}
+
+/* Nothing in flight: time the open slot's linger and launch it, or sleep
+ * until there is work. */
+static void idle_wait(md5hip_batcher *b)
+{
+    struct slot *o = open_slot(b);
+    if (o && o->state == SLOT_OPEN && o->n > 0 && !o->writers) {
+        const uint64_t waited = now_us() - o->opened_us, l = linger_us(b);
+        if (waited >= l) slot_try_launch(b, o);    /* lingered long enough */
+        else wait_work_us(b, l - waited);
+    } else {
+        pthread_cond_wait(&b->work_cv, &b->mu);
+    }
+}
+
+/* The device is busy: get open slot `o`'s descriptors over and its plan
+ * made now, once no chunk arrived since the last poll, so its launch is
+ * only the kernel when the running one retires. */
+static void prepare_ahead(struct slot *o)
+{
+    if (o->state != SLOT_OPEN || o->mode == MODE_FIXED || o->n <= o->planned_n) return;
+    if (o->n == o->seen_n) {
+        const int e = slot_prepare(o);
+        if (e && !o->err) o->err = e;
+    }
+    o->seen_n = o->n;
+}
+
+/* Open slot `o` planned and quiet, the pipeline at its target, and the last
+ * launch due to end within min(2 ms, a quarter of a launch): chain it there
+ * (its kernel waits on that launch's event).  Not behind a launch overdue by
+ * more than that: its end is unknown, and the open slot keeps coalescing
+ * until it retires.  Did it chain? */
+static int chain_open(md5hip_batcher *b, struct slot *o)
+{
+    if (!(b->chain && o->state == SLOT_OPEN && o->n && !o->writers && !o->err && !o->chain_ev &&
+          o->mode != MODE_FIXED && o->planned_n == o->n && b->inflight == b->target &&
+          b->launch_ema_us > 0))
+        return 0;
+    struct slot *last = NULL;
+    for (uint32_t k = 0; k < b->nslots; k++)
+        if (b->s[k].state == SLOT_INFLIGHT && (!last || b->s[k].launched_us > last->launched_us))
+            last = &b->s[k];
+    const double lead = b->launch_ema_us / 4 < CHAIN_LEAD_MAX_US ? b->launch_ema_us / 4
+                                                                 : CHAIN_LEAD_MAX_US;
+    const uint64_t end = last ? last->launched_us + (uint64_t)b->launch_ema_us : 0;
+    const uint64_t now = now_us();
+    if (!(last && (double)now + lead >= (double)end && (double)now <= (double)end + lead)) return 0;
+    o->chain_ev = last->kdone;
+    o->chain_at = end > now ? end : now;
+    o->chain_overlap = b->chain == 2 && last->mode != MODE_FIXED &&
+                       last->kind == MD5HIP_DIGEST_MD5 && o->kind == MD5HIP_DIGEST_MD5 &&
+                       last->plan_var == MD5HIP_DESC_BALANCED &&
+                       o->plan_var == MD5HIP_DESC_BALANCED;
+    slot_try_launch(b, o);
+    return 1;
+}
+
+/* Poll interval: idle_us (20 -> 200 us) while nobody waits; blocked callers
+ * pin it at 10 us (a short launch is not delivered up to 200 us late)
+ * unless each of their launches has a watcher of its own: callers on an
+ * open slot (it goes when a launch retires), or on a launch with no watcher
+ * yet or whose watcher's spin ran out. */
+static unsigned poll_interval_us(md5hip_batcher *b, unsigned idle_us)
+{
+    int fast = b->slot_waiters > 0;
+    for (uint32_t k = 0; k < b->nslots; k++)
+        fast |= b->s[k].nwait && !(b->s[k].state == SLOT_INFLIGHT && b->s[k].watch == WATCH_ACTIVE);
+    b->poll_fast = fast;
+    return fast ? 10u : idle_us;
+}
+
 static void *progress_main(void *arg)
 {
     md5hip_batcher *b = arg;
@@ -792,86 +966,20 @@ static void *progress_main(void *arg)
     pthread_mutex_lock(&b->mu);
     unsigned idle_us = 20;
     while (!b->stop) {
-        int any = 0;
         b->poll_fast = 0;
-        for (uint32_t k = 0; k < b->nslots; k++) {
-            struct slot *sl = &b->s[k];
-            if (sl->state != SLOT_INFLIGHT) continue;
-            const hipError_t e = launch_status(sl->done, sl->inject);
-            if (e == hipErrorNotReady) continue;
-            slot_complete(b, sl, e);
-            any = 1;
-        }
-        if (any) {
-            if (b->open >= 0) slot_try_launch(b, &b->s[b->open]);
+        if (retire_finished(b)) {
+            try_open(b);
             idle_us = 20;
-            continue;
-        }
-        if (b->inflight == 0) {
-            struct slot *o = b->open >= 0 ? &b->s[b->open] : NULL;
-            if (o && o->state == SLOT_OPEN && o->n > 0 && !o->writers) {
-                const uint64_t waited = now_us() - o->opened_us, l = linger_us(b);
-                if (waited >= l) slot_try_launch(b, o);    /* lingered long enough */
-                else wait_work_us(b, l - waited);
-            } else {
-                pthread_cond_wait(&b->work_cv, &b->mu);
-            }
+        } else if (b->inflight == 0) {
+            idle_wait(b);
             idle_us = 20;
         } else {
-            /* the device is busy: get the open slot's descriptors over and its
-             * plan made now, once no chunk arrived since the last poll, so
-             * its launch is only the kernel when the running one retires */
-            if (b->open >= 0) {
-                struct slot *o = &b->s[b->open];
-                if (o->state == SLOT_OPEN && o->mode != MODE_FIXED && o->n > o->planned_n) {
-                    if (o->n == o->seen_n) {
-                        const int e = slot_prepare(b, o);
-                        if (e && !o->err) o->err = e;
-                    }
-                    o->seen_n = o->n;
-                }
-                /* planned and quiet, the pipeline at its target, and the last
-                 * launch due to end within min(2 ms, a quarter of a launch):
-                 * chain it there (its kernel waits on that launch's event).
-                 * Not behind a launch overdue by more than that: its end is
-                 * unknown, and the open slot keeps coalescing until it retires */
-                if (b->chain && o->state == SLOT_OPEN && o->n && !o->writers && !o->err && !o->chain_ev &&
-                    o->mode != MODE_FIXED && o->planned_n == o->n && b->inflight == b->target &&
-                    b->launch_ema_us > 0) {
-                    struct slot *last = NULL;
-                    for (uint32_t k = 0; k < b->nslots; k++)
-                        if (b->s[k].state == SLOT_INFLIGHT && (!last || b->s[k].launched_us > last->launched_us))
-                            last = &b->s[k];
-                    const double lead = b->launch_ema_us / 4 < CHAIN_LEAD_MAX_US ? b->launch_ema_us / 4
-                                                                                 : CHAIN_LEAD_MAX_US;
-                    const uint64_t end = last ? last->launched_us + (uint64_t)b->launch_ema_us : 0;
-                    const uint64_t now = now_us();
-                    if (last && (double)now + lead >= (double)end && (double)now <= (double)end + lead) {
-                        o->chain_ev = last->kdone;
-                        o->chain_at = end > now ? end : now;
-                        o->chain_overlap = b->chain == 2 && last->mode != MODE_FIXED &&
-                                           last->kind == MD5HIP_DIGEST_MD5 && o->kind == MD5HIP_DIGEST_MD5 &&
-                                           last->plan_var == MD5HIP_DESC_BALANCED &&
-                                           o->plan_var == MD5HIP_DESC_BALANCED;
-                        slot_try_launch(b, o);
-                    }
-                }
+            struct slot *o = open_slot(b);
+            if (o) {
+                prepare_ahead(o);
+                chain_open(b, o);
             }
-            /* poll interval: 20 -> 200 us while nobody waits; blocked callers
-             * pin it at 10 us (a short launch is not delivered up to 200 us
-             * late) unless each of their launches has a watcher of its own:
-             * callers on an open slot (it goes when a launch retires), or on
-             * a launch with no watcher yet or whose watcher's spin ran out */
-            int fast = b->slot_waiters > 0;
-            for (uint32_t k = 0; k < b->nslots; k++)
-                fast |= b->s[k].nwait && !(b->s[k].state == SLOT_INFLIGHT && b->s[k].watch == WATCH_ACTIVE);
-            b->poll_fast = fast;
-            const unsigned us = fast ? 10u : idle_us;
-            struct timespec ts;
-            clock_gettime(CLOCK_REALTIME, &ts);
-            ts.tv_nsec += (long)us * 1000;
-            if (ts.tv_nsec >= 1000000000L) { ts.tv_sec++; ts.tv_nsec -= 1000000000L; }
-            pthread_cond_timedwait(&b->work_cv, &b->mu, &ts);
+            wait_work_us(b, poll_interval_us(b, idle_us));
             if (idle_us < 200) idle_us += 20;
         }
     }
@@ -896,8 +1004,7 @@ static void *progress_main(void *arg)
  * every state change that ends one (retire, launch) is made under b->mu and
  * broadcast or signalled, so no wake-up is lost.
  * ------------------------------------------------------------------------ */
-enum { WATCH_SPIN_US = 300, WATCH_LEAD_US = 200 };   /* WATCH_POLICY_SPIN */
-enum { WATCH_TAIL_US = 50, WATCH_TAIL_SPIN_US = 150 };  /* WATCH_POLICY_TAIL */
+enum { WATCH_TAIL_US = 50, WATCH_TAIL_SPIN_US = 150 };
 
 static void cpu_relax(void)
 {
@@ -919,44 +1026,32 @@ static void watch_sleep(md5hip_batcher *b, struct slot *sl, uint64_t us)
     if (old > 2000) (void)prctl(PR_SET_TIMERSLACK, (unsigned long)old, 0, 0, 0);
 }
 
-/* Watch in-flight slot `sl` (mu held on entry and exit, watch == NONE).
- * The policy (b->watch_policy, MD5HIP_WATCH at create; profiles/r05e/):
- *   TAIL   (default) sleep on the slot until 50 us before the launch is due
- *          (recent launches' wall time), then poll its event for at most
- *          150 us; past that the watcher gives up and sleeps too, and the
- *          progress thread (polling every 10 us meanwhile) retires it.  At
- *          8 callers a call costs its thread 33-39 us of CPU instead of
- *          SPIN's 122 (the whole ~150 us launch polled), same latency;
- *   SPIN   round 4: a launch due within 300 us is polled for up to 500 us
- *          (a longer one slept through until 200 us before its end);
- *   BLOCK  hipEventSynchronize on a blocking-sync event: measured, not
- *          kept -- the wake-up after the interrupt costs ~1 ms per call
- *          and ~190 us of CPU (r05e/asio_watch.json). */
+/* Watch in-flight slot `sl` (mu held on entry and exit, watch == NONE):
+ * sleep on the slot until 50 us before the launch is due (recent launches'
+ * wall time), then poll its event for at most 150 us; past that the watcher
+ * gives up and sleeps too, and the progress thread (polling every 10 us
+ * meanwhile) retires it.  Two other policies were measured against this one
+ * and removed (profiles/r05e/asio_watch.json, profiles/r05f/; git history):
+ * polling a launch due within 300 us for up to 500 us cost a call's thread
+ * 122 us of CPU at 8 callers instead of 33-39, same latency; and
+ * hipEventSynchronize on a blocking-sync event woke up ~1 ms late per call
+ * for ~190 us of CPU. */
 static void watch_launch(md5hip_batcher *b, struct slot *sl)
 {
     const uint64_t gen = sl->gen;
-    const int pol = b->watch_policy;
-    const uint64_t spin = pol == WATCH_POLICY_SPIN ? WATCH_SPIN_US : WATCH_TAIL_US;
-    const uint64_t lead = pol == WATCH_POLICY_SPIN ? WATCH_LEAD_US : WATCH_TAIL_US;
     sl->watch = WATCH_ACTIVE;
-    for (; pol != WATCH_POLICY_BLOCK;) {        /* long launch: sleep most of it */
+    for (;;) {                                  /* long launch: sleep most of it */
         const uint64_t now = now_us(), end = sl->launched_us + (uint64_t)b->launch_ema_us;
-        if (end <= now + spin) break;
-        watch_sleep(b, sl, end - now - lead);
+        if (end <= now + WATCH_TAIL_US) break;
+        watch_sleep(b, sl, end - now - WATCH_TAIL_US);
         if (sl->state != SLOT_INFLIGHT || sl->gen != gen) return;     /* retired meanwhile */
     }
     const hipEvent_t ev = sl->done;
     const int inject = sl->inject;
     pthread_mutex_unlock(&b->mu);
-    hipError_t e = hipErrorNotReady;
-    if (pol != WATCH_POLICY_BLOCK) {
-        const uint64_t t0 = now_us(), limit = pol == WATCH_POLICY_SPIN ? WATCH_SPIN_US + WATCH_LEAD_US
-                                                                       : WATCH_TAIL_SPIN_US;
-        while ((e = launch_status(ev, inject)) == hipErrorNotReady && now_us() - t0 < limit) cpu_relax();
-    } else {
-        e = hipEventSynchronize(ev);
-        if (e == hipSuccess && inject) e = hipErrorLaunchFailure;
-    }
+    hipError_t e;
+    const uint64_t t0 = now_us();
+    while ((e = launch_status(ev, inject)) == hipErrorNotReady && now_us() - t0 < WATCH_TAIL_SPIN_US) cpu_relax();
     pthread_mutex_lock(&b->mu);
     /* the same launch still in flight? (the progress thread may have retired
      * it, and the slot may even be in flight again with other work: then
@@ -967,7 +1062,7 @@ static void watch_launch(md5hip_batcher *b, struct slot *sl)
         return;
     }
     slot_complete(b, sl, e);
-    if (b->open >= 0) slot_try_launch(b, &b->s[b->open]);
+    try_open(b);
     pthread_cond_broadcast(&b->work_cv);
 }
 
@@ -1051,11 +1146,7 @@ void md5hip_batcher_destroy(md5hip_batcher *b)
     if (b->progress_started) {
         pthread_mutex_lock(&b->mu);
         /* launch what is still open so every ticket completes, then drain */
-        if (b->open >= 0) {
-            struct slot *o = &b->s[b->open];
-            o->flush = 1;
-            slot_try_launch(b, o);
-        }
+        flush_open(b);
         while (b->inflight) pthread_cond_wait(&b->done_cv, &b->mu);
         b->stop = 1;
         pthread_cond_broadcast(&b->work_cv);
@@ -1094,15 +1185,6 @@ static int batcher_new(int device, uint64_t slice_bytes, uint32_t nslots, uint64
     b->linger_max_us = 5000;
     b->chain = 2;
     b->open = -1;
-    {
-        const char *w = getenv("MD5HIP_WATCH");      /* spin / tail / block (A/B of the watcher) */
-        b->watch_policy = !w ? WATCH_POLICY_TAIL
-                        : !strcmp(w, "spin") ? WATCH_POLICY_SPIN
-                        : !strcmp(w, "block") ? WATCH_POLICY_BLOCK : WATCH_POLICY_TAIL;
-    }
-    /* BLOCK's watcher sleeps in hipEventSynchronize: blocking-sync events */
-    const unsigned done_flags = hipEventDisableTiming |
-                                (b->watch_policy == WATCH_POLICY_BLOCK ? hipEventBlockingSync : 0u);
     b->s = calloc(nslots, sizeof *b->s);
     /* ticket 0 = "nothing": complete at once */
     if (!b->s || tk_ring_init(&b->tk, 1)) { rc = -ENOMEM; goto fail; }
@@ -1111,7 +1193,7 @@ static int batcher_new(int device, uint64_t slice_bytes, uint32_t nslots, uint64
     for (uint32_t k = 0; k < nslots; k++) {
         struct slot *sl = &b->s[k];
         CK(hipStreamCreateWithFlags(&sl->stream, hipStreamNonBlocking));
-        CK(hipEventCreateWithFlags(&sl->done, done_flags));
+        CK(hipEventCreateWithFlags(&sl->done, hipEventDisableTiming));
         CK(hipEventCreateWithFlags(&sl->kdone, hipEventDisableTiming));
         CK(hipHostMalloc((void **)&sl->h_data, b->cap, hipHostMallocDefault));
         /* fine-grained: a small slot's kernel reads them in place (slot_prepare) */
@@ -1179,15 +1261,29 @@ int md5hip_queue_create(int device, uint64_t max_chunks, uint32_t nslots, md5hip
     return batcher_new(device, 16ull << 20, nslots, max_chunks, out);
 }
 
+/* An entry that may launch the open slot from the caller's thread
+ * (slot_enqueue's device-keyed state: the BALANCED counter, CU counts) runs
+ * on the batcher's device, like submit -- a pool waits on a ticket of one
+ * device from a thread whose current device is another.  In: that device,
+ * then b->mu; out: both back. */
+static int batcher_enter(md5hip_batcher *b, struct dev_guard *g)
+{
+    if (dev_enter(g, b->device)) return -ENODEV;
+    pthread_mutex_lock(&b->mu);
+    return 0;
+}
+
+static void batcher_leave(md5hip_batcher *b, const struct dev_guard *g)
+{
+    pthread_mutex_unlock(&b->mu);
+    dev_leave(g);
+}
+
 /* Wait until nothing is open or in flight (mu held). */
 static void drain(md5hip_batcher *b)
 {
     for (;;) {
-        if (b->open >= 0) {
-            struct slot *o = &b->s[b->open];
-            o->flush = 1;
-            slot_try_launch(b, o);
-        }
+        flush_open(b);
         int busy = 0;
         for (uint32_t k = 0; k < b->nslots; k++) busy |= b->s[k].state != SLOT_FREE;
         if (!busy) return;
@@ -1201,13 +1297,11 @@ int md5hip_batcher_set_digest(md5hip_batcher *b, int kind, uint32_t fastcrc)
     const int u = md5hip_digest_usable(kind, fastcrc);
     if (u) return u;
     struct dev_guard g;
-    if (dev_enter(&g, b->device)) return -ENODEV;  /* drain may launch the open slot */
-    pthread_mutex_lock(&b->mu);
+    if (batcher_enter(b, &g)) return -ENODEV;    /* drain may launch the open slot */
     drain(b);                                    /* never change kind under queued work */
     b->kind = kind;
     b->fastcrc = fastcrc;
-    pthread_mutex_unlock(&b->mu);
-    dev_leave(&g);
+    batcher_leave(b, &g);
     return 0;
 }
 
@@ -1234,12 +1328,10 @@ int md5hip_batcher_set_inflight(md5hip_batcher *b, uint32_t target)
 {
     if (!b || target == 0 || target > b->nslots) return -EINVAL;
     struct dev_guard g;
-    if (dev_enter(&g, b->device)) return -ENODEV;
-    pthread_mutex_lock(&b->mu);
+    if (batcher_enter(b, &g)) return -ENODEV;
     b->target = target;
-    if (b->open >= 0) slot_try_launch(b, &b->s[b->open]);
-    pthread_mutex_unlock(&b->mu);
-    dev_leave(&g);
+    try_open(b);
+    batcher_leave(b, &g);
     return 0;
 }
 
@@ -1291,25 +1383,8 @@ int md5hip_batcher_get_stats(md5hip_batcher *b, struct md5hip_batcher_stats *out
 }
 
 /* ------------------------------------------------------------------------
- * Chunk sources
+ * Submission (the host chunk sources themselves: md5_source.h)
  * ------------------------------------------------------------------------ */
-/* struct md5hip_src (md5_internal.h); the host kinds, PTRS and IOV, as
- * segments: chunk i is entry s->first + i of the caller's arrays */
-static uint64_t src_nseg(const struct md5hip_src *s, uint64_t i)
-{
-    i += s->first;
-    return s->kind == MD5HIP_SRC_PTRS ? 1 : s->seg_first[i + 1] - s->seg_first[i];
-}
-
-static void src_seg(const struct md5hip_src *s, uint64_t i, uint64_t k, const void **base,
-                    uint32_t *len)
-{
-    i += s->first;
-    if (s->kind == MD5HIP_SRC_PTRS) { *base = s->ptrs[i]; *len = s->lens[i]; return; }
-    *base = s->segs[s->seg_first[i] + k].base;
-    *len = s->segs[s->seg_first[i] + k].len;
-}
-
 /* Every non-empty segment of the call in registered memory? */
 static int src_registered(const struct md5hip_src *s, uint64_t n)
 {
@@ -1326,176 +1401,23 @@ static int src_registered(const struct md5hip_src *s, uint64_t n)
     return ok;
 }
 
-static void src_copy(const struct md5hip_src *s, uint64_t i, unsigned char *dst)
+/* Chunk key k = (len >> 6) + 1 into the key histogram hh and its running
+ * values (md5hip.h md5hip_plan_hist): the largest key, whether a key past
+ * MD5HIP_HIST_KMAX was seen (host sort instead), and whether the keys so far
+ * were non-increasing (then no order is built).  reserve_device passes
+ * locals, so its loop keeps them in registers. */
+static inline void hist_add(uint32_t *hh, uint32_t key, uint32_t *last, uint32_t *kmax, int *unsorted, int *hovf)
 {
-    i += s->first;
-    if (s->kind == MD5HIP_SRC_PTRS) {
-        if (s->lens[i]) memcpy(dst, s->ptrs[i], s->lens[i]);
-        return;
-    }
-    for (uint64_t j = s->seg_first[i]; j < s->seg_first[i + 1]; j++) {
-        if (s->segs[j].len) memcpy(dst, s->segs[j].base, s->segs[j].len);
-        dst += s->segs[j].len;
-    }
-}
-
-/* Bytes [a, a + len) of chunk i to dst. */
-static void src_copy_range(const struct md5hip_src *s, uint64_t i, uint64_t a, uint64_t len, unsigned char *dst)
-{
-    if (!len) return;
-    i += s->first;
-    if (s->kind == MD5HIP_SRC_PTRS) {
-        memcpy(dst, (const unsigned char *)s->ptrs[i] + a, len);
-        return;
-    }
-    for (uint64_t j = s->seg_first[i]; j < s->seg_first[i + 1] && len; j++) {
-        const uint64_t sl = s->segs[j].len;
-        if (a >= sl) {
-            a -= sl;
-            continue;
-        }
-        const uint64_t take = sl - a < len ? sl - a : len;
-        memcpy(dst, (const unsigned char *)s->segs[j].base + a, take);
-        dst += take;
-        len -= take;
-        a = 0;
+    *unsorted |= key > *last;
+    *last = key;
+    if (key > MD5HIP_HIST_KMAX) {
+        *hovf = 1;
+    } else {
+        hh[key]++;
+        if (key > *kmax) *kmax = key;
     }
 }
 
-/* What a digest reads of an L-byte chunk: netcache's CRC-32 with a fastcrc
- * window F < L reads only the first and the last F bytes (blk_io.c:408-424),
- * so for L > 2F only those 2F bytes are staged and sent, as ONE 2F-byte
- * chunk whose own fastcrc digest is the same crc(head) ^ crc(tail) (a 16 KiB
- * block with F = 128: 256 B over PCIe instead of 16 KiB).  Up to 2F, and
- * for F = 0 (MD5 too), the whole chunk: never more than L bytes, so a chunk
- * that passes submit()'s size check always fits an empty slot. */
-static inline uint64_t staged_len(uint32_t F, uint64_t L) { return F && L > 2ull * F ? 2ull * F : L; }
-
-/* Table entries a zero-copy chunk of `ns` segments may take: one per
- * segment, one more when it is sent as two windows (one segment may hold
- * both), plus two spare.  submit() sends a chunk zero-copy only if this fits
- * an empty slot (win = 1, whatever the digest), so reserve() always places
- * it. */
-static inline uint64_t zc_pieces(uint64_t ns, int win) { return ns + (win ? 1 : 0) + 2; }
-
-/* chunk i as staged: whole, or its head and tail windows */
-static void src_copy_staged(const struct md5hip_src *s, uint64_t i, uint32_t F, unsigned char *dst)
-{
-    const uint64_t L = F ? md5hip_src_len(s, i) : 0;
-    if (staged_len(F, L) == L) {
-        src_copy(s, i, dst);
-        return;
-    }
-    src_copy_range(s, i, 0, F, dst);
-    src_copy_range(s, i, L - F, F, dst + F);
-}
-
-/* Large host copies are fanned out: one thread's memcpy from pageable
- * memory into pinned staging runs ~15 GB/s, well below PCIe,
- * so a copy past 8 MiB is cut into parts of at least 2 MiB for
- * MD5HIP_GATHER_THREADS threads (default 4, at most 32; the calling thread
- * takes the first part, and any part whose thread could not be created). */
-static pthread_once_t g_gather_once = PTHREAD_ONCE_INIT;
-static int g_gather_threads = 4;
-
-static void gather_threads_init(void)
-{
-    const char *e = getenv("MD5HIP_GATHER_THREADS");
-    if (e && *e) {
-        const int t = atoi(e);
-        g_gather_threads = t < 1 ? 1 : t > 32 ? 32 : t;
-    }
-}
-
-#define GATHER_SPLIT_MIN (8ull << 20)   /* bytes per range before it is split */
-#define GATHER_PART_MIN (2ull << 20)    /* and at least this many bytes per part */
-enum { FAN_MAX = 32 };
-
-/* how many parts for `bytes` in `units` indivisible pieces: 1 .. FAN_MAX */
-static uint64_t fan_parts(uint64_t bytes, uint64_t units)
-{
-    pthread_once(&g_gather_once, gather_threads_init);
-    uint64_t T = (uint64_t)g_gather_threads;
-    if (bytes < GATHER_SPLIT_MIN) T = 1;
-    if (T > bytes / GATHER_PART_MIN) T = bytes / GATHER_PART_MIN ? bytes / GATHER_PART_MIN : 1;
-    if (T > units) T = units ? units : 1;
-    return T < 1 ? 1 : T > FAN_MAX ? FAN_MAX : T;
-}
-
-/* run(part t) for the T <= FAN_MAX parts of `size` bytes each at `parts` */
-static void fan_out(void *(*run)(void *), void *parts, size_t size, uint64_t T)
-{
-    pthread_t tid[FAN_MAX];
-    int started[FAN_MAX] = {0};
-    for (uint64_t t = 1; t < T; t++)
-        started[t] = pthread_create(&tid[t], NULL, run, (char *)parts + t * size) == 0;
-    run(parts);
-    for (uint64_t t = 1; t < T; t++) {
-        if (started[t]) pthread_join(tid[t], NULL);
-        else run((char *)parts + t * size);      /* no thread: copy it here */
-    }
-}
-
-/* Host gather of chunks [first, first + m) to dst + off[j], the range
- * [lo, used) of the staging cut by bytes at chunk boundaries. */
-struct gather_part {
-    const struct md5hip_src *src;
-    uint64_t first, jlo, jhi;
-    const uint64_t *off;
-    unsigned char *dst;
-    uint32_t win;                         /* fastcrc window of a CRC-32 slot (staged_len), else 0 */
-};
-
-static void *gather_run(void *arg)
-{
-    const struct gather_part *p = arg;
-    for (uint64_t j = p->jlo; j < p->jhi; j++) src_copy_staged(p->src, p->first + j, p->win, p->dst + p->off[j]);
-    return NULL;
-}
-
-static void gather_range(const struct md5hip_src *src, uint64_t first, uint64_t m,
-                         const uint64_t *off, unsigned char *dst, uint64_t lo, uint64_t used, uint32_t win)
-{
-    const uint64_t bytes = used - lo, T = fan_parts(bytes, m);
-    struct gather_part part[FAN_MAX];
-    uint64_t j = 0;
-    for (uint64_t t = 0; t < T; t++) {      /* part t: chunks whose offset < lo + (t+1) * bytes / T */
-        const uint64_t lim = t + 1 == T ? UINT64_MAX : lo + (t + 1) * bytes / T;
-        part[t] = (struct gather_part){src, first, j, j, off, dst, win};
-        while (j < m && off[j] < lim) j++;
-        part[t].jhi = j;
-    }
-    fan_out(gather_run, part, sizeof part[0], T);
-}
-
-/* memcpy of `bytes`, cut evenly */
-struct copy_part {
-    unsigned char *dst;
-    const unsigned char *src;
-    uint64_t len;
-};
-
-static void *copy_run(void *arg)
-{
-    const struct copy_part *c = arg;
-    memcpy(c->dst, c->src, c->len);
-    return NULL;
-}
-
-static void copy_parallel(void *dst, const void *src, uint64_t bytes)
-{
-    const uint64_t T = fan_parts(bytes, UINT64_MAX);
-    struct copy_part part[FAN_MAX];
-    for (uint64_t t = 0; t < T; t++) {
-        const uint64_t a = bytes * t / T, z = bytes * (t + 1) / T;
-        part[t] = (struct copy_part){(unsigned char *)dst + a, (const unsigned char *)src + a, z - a};
-    }
-    fan_out(copy_run, part, sizeof part[0], T);
-}
-
-/* ------------------------------------------------------------------------
- * Submission
- * ------------------------------------------------------------------------ */
 /* Device-resident chunks [i, i + m) into slot `sl` (mu held, m fits): the
  * descriptors, payload and key histogram in one pass with the running
  * values in registers -- no bytes to stage.  While a burst of C3 vectors is
@@ -1505,7 +1427,11 @@ static void copy_parallel(void *dst, const void *src, uint64_t bytes)
  * --hip-trace, profiles/r04k/).  Neither threads (slower at every count,
  * profiles/r04f/) nor non-temporal stores (2.4x in isolation,
  * profiles/r04i/, no change in the submission, profiles/r04j/) shortened
- * it, so it stays one plain pass on the calling thread. */
+ * it, so it stays one plain pass on the calling thread.  A function of its
+ * own on a 64-byte boundary: inlined into submit() the loop moved with every
+ * edit before it, and sitting across three 64-byte lines instead of two it
+ * cost the call 6 % (profiles/batcher_split/ab.json). */
+__attribute__((noinline, aligned(64)))
 static void reserve_device(md5hip_batcher *b, struct slot *sl, const struct md5hip_src *src, uint64_t i,
                            uint64_t m)
 {
@@ -1525,15 +1451,7 @@ static void reserve_device(md5hip_batcher *b, struct slot *sl, const struct md5h
         hl[k] = L;
         pay += L;
         unl += ((p & 127u) != 0 && (p & 15u) == 0) ? L : 0;
-        const uint32_t key = (L >> 6) + 1;           /* L < 2^32: no overflow */
-        unsorted |= key > last;
-        last = key;
-        if (key > MD5HIP_HIST_KMAX) {
-            hovf = 1;
-        } else {
-            hh[key]++;
-            if (key > kmax) kmax = key;
-        }
+        hist_add(hh, (L >> 6) + 1, &last, &kmax, &unsorted, &hovf);   /* L < 2^32: no overflow */
     }
     sl->last_key = last;
     sl->hkmax = kmax;
@@ -1541,8 +1459,7 @@ static void reserve_device(md5hip_batcher *b, struct slot *sl, const struct md5h
     sl->hovf = hovf;
     sl->payload += pay;
     sl->unlined += unl;
-    sl->load += pay + 64 * m;
-    __atomic_store_n(&b->load_bytes, b->load_bytes + pay + 64 * m, __ATOMIC_RELAXED);
+    load_add(b, sl, pay + 64 * m);
     sl->n += m;
 }
 
@@ -1576,6 +1493,32 @@ static void zc_piece(struct slot *sl, int dev, const void *p, uint32_t len, long
     }
 }
 
+/* Chunk j of `src` -- L bytes, E of them staged: all of it, or its two
+ * F-byte windows -- into the slot's zero-copy tables at staging offset
+ * sl->used (mu and g_reg_lock held).  0; 1 when the tables have no room for
+ * it; -EFAULT when a piece is registered no longer. */
+static int reserve_zc(md5hip_batcher *b, struct slot *sl, const struct md5hip_src *src, uint64_t j,
+                      uint64_t L, uint64_t E, uint32_t F)
+{
+    const int win = E != L;
+    const uint64_t need = zc_pieces(src_nseg(src, j), win);
+    if (sl->nseg + need > b->segcap || sl->ndma + need > b->segcap) return 1;
+    const uint64_t ra[2] = {0, win ? L - F : 0}, rl[2] = {win ? F : L, win ? F : 0};
+    uint64_t at = sl->used;
+    for (int w = 0; w < 2; w++) {
+        struct src_walk walk = src_walk_range(src, j, ra[w], rl[w]);
+        const void *p;
+        uint32_t take;
+        while (src_walk_next(&walk, &p, &take)) {
+            const long r = reg_find((uintptr_t)p, take);
+            if (r < 0) return -EFAULT;
+            zc_piece(sl, b->device, p, take, r, at);
+            at += take;
+        }
+    }
+    return 0;
+}
+
 /* Reserve chunks [i, n) of `src` into the open slot (mu held): descriptors,
  * staging offsets, zero-copy tables.  Returns the number reserved (the slot
  * is marked full when a chunk did not fit) or -errno.  A CRC-32 slot with a
@@ -1583,7 +1526,6 @@ static void zc_piece(struct slot *sl, int dev, const void *p, uint32_t len, long
 static long reserve(md5hip_batcher *b, struct slot *sl, const struct md5hip_src *src, uint64_t i,
                     uint64_t n, int zc)
 {
-    const int dev = b->device;
     const uint32_t F = sl->kind == MD5HIP_DIGEST_CRC32 ? sl->fastcrc : 0;
     uint64_t j = i;
     if (sl->n == 0 && i < n) sl->opened_us = now_us();
@@ -1597,62 +1539,24 @@ static long reserve(md5hip_batcher *b, struct slot *sl, const struct md5hip_src 
     while (j < n && sl->n < b->maxn) {
         const uint64_t L = md5hip_src_len(src, j);
         const uint64_t E = staged_len(F, L);
-        {   /* host bytes (device-resident chunks: reserve_device above) */
-            /* chunks packed on 128-B lines: the LDS-DMA loaders read 128-B
-             * stages, and a stage off the line shares a line with the next
-             * one (the nt policy is then off, md5_kernels.h) */
-            const uint64_t sz = (E + 127) & ~127ull;
-            if (sl->used + sz > b->cap) break;
-            if (zc) {
-                const uint64_t ns = src_nseg(src, j);
-                /* the chunk's byte ranges staged: all of it, or its windows */
-                const int win = E != L;
-                const uint64_t need = zc_pieces(ns, win);
-                if (sl->nseg + need > b->segcap || sl->ndma + need > b->segcap) break;
-                const uint64_t ra[2] = {0, win ? L - F : 0}, rl[2] = {win ? F : L, win ? F : 0};
-                uint64_t at = sl->used;
-                for (int w = 0; w < 2; w++) {
-                    uint64_t a = ra[w], left = rl[w];
-                    for (uint64_t q = 0; q < ns && left; q++) {
-                        const void *p;
-                        uint32_t len;
-                        src_seg(src, j, q, &p, &len);
-                        if (a >= len) {
-                            a -= len;
-                            continue;
-                        }
-                        const uint32_t take = (uint32_t)(len - a < left ? len - a : left);
-                        const void *pp = (const unsigned char *)p + a;
-                        a = 0;
-                        left -= take;
-                        const long r = reg_find((uintptr_t)pp, take);
-                        if (r < 0) {                           /* unregistered under us */
-                            pthread_rwlock_unlock(&g_reg_lock);
-                            return -EFAULT;
-                        }
-                        zc_piece(sl, dev, pp, take, r, at);
-                        at += take;
-                    }
-                }
-            }
-            sl->h_off[sl->n] = sl->used;
-            sl->used += sz;
+        /* chunks packed on 128-B lines: the LDS-DMA loaders read 128-B
+         * stages, and a stage off the line shares a line with the next
+         * one (the nt policy is then off, md5_kernels.h) */
+        const uint64_t sz = (E + 127) & ~127ull;
+        if (sl->used + sz > b->cap) break;
+        const int e = zc ? reserve_zc(b, sl, src, j, L, E, F) : 0;
+        if (e < 0) {                                /* unregistered under us */
+            pthread_rwlock_unlock(&g_reg_lock);
+            return e;
         }
+        if (e) break;
+        sl->h_off[sl->n] = sl->used;
+        sl->used += sz;
         sl->h_len[sl->n] = (uint32_t)E;
-        sl->load += E + 64;
         sl->payload += E;
-        __atomic_store_n(&b->load_bytes, b->load_bytes + E + 64, __ATOMIC_RELAXED);
-        {
-            const uint64_t k = (E >> 6) + 1;
-            if (k > sl->last_key) sl->unsorted = 1;
-            sl->last_key = k > UINT32_MAX ? UINT32_MAX : (uint32_t)k;
-            if (k > MD5HIP_HIST_KMAX) {
-                sl->hovf = 1;
-            } else {
-                sl->hh[k]++;
-                if (k > sl->hkmax) sl->hkmax = (uint32_t)k;
-            }
-        }
+        load_add(b, sl, E + 64);
+        /* E < 2^32 (submit's size check): the key fits */
+        hist_add(sl->hh, (uint32_t)(E >> 6) + 1, &sl->last_key, &sl->hkmax, &sl->unsorted, &sl->hovf);
         sl->n++;
         j++;
     }
@@ -1660,6 +1564,31 @@ static long reserve(md5hip_batcher *b, struct slot *sl, const struct md5hip_src 
     if (j < n) sl->full = 1;
     return (long)(j - i);
 }
+
+/* What a submission asks for beside its chunks; an entry names what it sets,
+ * the rest is 0 / NULL.
+ *   digests, on_device   where the digests go: a host array, or device memory
+ *   async   0 = synchronous (returns when the digests are delivered);
+ *           1 = asynchronous (*ticket; the slot may linger and coalesce);
+ *           2 = asynchronous but launched at once like a synchronous call
+ *               (the caller waits on *ticket right away: the pool's
+ *               synchronous entries)
+ *   kind    KIND_BATCHER: the batcher's current digest kind; else this
+ *           submission's own, with `fastcrc` (it never changes the
+ *           batcher's setting)
+ *   after   != NULL: *after is the producer's stream (NULL there = the null
+ *           stream) -- every slot taking chunks of this submission waits on
+ *           the producer's work enqueued so far before its kernel (an event
+ *           recorded on *after, waited on by the slot's stream) */
+enum { KIND_BATCHER = -1 };
+struct sub_opt {
+    unsigned char *digests;
+    int on_device, async;
+    uint64_t *ticket;
+    int kind;
+    uint32_t fastcrc;
+    const hipStream_t *after;
+};
 
 /* One submission between sub_begin and sub_end: the caller's device (entered
  * by the engine before sub_begin), its ticket and its digest kind. */
@@ -1670,25 +1599,23 @@ struct sub {
     uint32_t fastcrc, dsz;
 };
 
-/* Takes b->mu and opens the submission: the digest kind (< 0: the
- * batcher's), a ticket, `after` checked to be a stream of this device.  On
- * an error nothing is held any more: mu released, the caller's device put
- * back. */
-static int sub_begin(md5hip_batcher *b, struct sub *s, int kind, uint32_t fastcrc, const hipStream_t *after)
+/* Takes b->mu and opens the submission: the digest kind, a ticket,
+ * `after` checked to be a stream of this device.  On an error nothing is
+ * held any more: mu released, the caller's device put back. */
+static int sub_begin(md5hip_batcher *b, struct sub *s, const struct sub_opt *o)
 {
     pthread_mutex_lock(&b->mu);
-    s->kind = kind < 0 ? b->kind : kind;
-    s->fastcrc = kind < 0 ? b->fastcrc : fastcrc;
+    s->kind = o->kind < 0 ? b->kind : o->kind;
+    s->fastcrc = o->kind < 0 ? b->fastcrc : o->fastcrc;
     s->dsz = md5hip_digest_size(s->kind);
     s->t = 0;
     int rc = b->failed ? b->failed : tk_ring_new(&b->tk, &s->t);
-    if (rc == 0 && after && hipEventRecord(b->after_ev, *after) != hipSuccess) {
+    if (rc == 0 && o->after && hipEventRecord(b->after_ev, *o->after) != hipSuccess) {
         tk_ring_put(&b->tk, s->t, 0);
         rc = -EINVAL;                              /* not a stream of this device */
     }
     if (rc) {
-        pthread_mutex_unlock(&b->mu);
-        dev_leave(&s->g);
+        batcher_leave(b, &s->g);
         return rc;
     }
     b->st.submissions++;
@@ -1706,9 +1633,23 @@ static int sub_end(md5hip_batcher *b, struct sub *s, int rc, uint64_t *ticket, i
         const int err = wait_ticket(b, s->t);
         if (!rc) rc = err;
     }
-    pthread_mutex_unlock(&b->mu);
-    dev_leave(&s->g);
+    batcher_leave(b, &s->g);
     return rc;
+}
+
+/* A submitter's copy into slot `sl` runs outside b->mu, between these two:
+ * the slot is held by a writer count (slot_try_launch waits for
+ * writers == 0) while other submitters reserve behind it. */
+static void write_begin(md5hip_batcher *b, struct slot *sl)
+{
+    sl->writers++;
+    pthread_mutex_unlock(&b->mu);
+}
+
+static void write_end(md5hip_batcher *b, struct slot *sl)
+{
+    pthread_mutex_lock(&b->mu);
+    sl->writers--;
 }
 
 /* The producer's work enqueued so far, before slot `sl`'s kernel (mu held).
@@ -1722,23 +1663,11 @@ static void slot_after(md5hip_batcher *b, struct slot *sl, const hipStream_t *af
         sl->err = -EIO;
 }
 
-/* The submission engine.
- *   async   0 = synchronous (returns when the digests are delivered);
- *           1 = asynchronous (*ticket; the slot may linger and coalesce);
- *           2 = asynchronous but launched at once like a synchronous call
- *               (the caller waits on *ticket right away: the pool's
- *               synchronous entries)
- *   kind    < 0: the batcher's current digest kind; else this submission's
- *           own (it never changes the batcher's setting)
- *   after   != NULL: *after is the producer's stream (NULL there = the null
- *           stream) -- every slot taking chunks of this submission waits on
- *           the producer's work enqueued so far before its kernel (an event
- *           recorded on *after, waited on by the slot's stream) */
-static int submit(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, unsigned char *digests,
-                  int on_device, int async, uint64_t *ticket, int kind, uint32_t fastcrc,
-                  const hipStream_t *after)
+/* The submission engine: chunks [0, n) of a PTRS, IOV or DEVICE source into
+ * the open slot, as many slots as they take. */
+static int submit(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, const struct sub_opt *o)
 {
-    const int urgent = async != 1, dev_src = src->kind == MD5HIP_SRC_DEVICE;
+    const int urgent = o->async != 1, dev_src = src->kind == MD5HIP_SRC_DEVICE;
     for (uint64_t i = 0; !dev_src && i < n; i++) {      /* device chunks: uint32 lengths, no staging */
         const uint64_t L = md5hip_src_len(src, i);
         if (L > 0xffffffffull) return -E2BIG;
@@ -1757,24 +1686,18 @@ static int submit(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, u
             if (zc_pieces(src_nseg(src, i), 1) > b->segcap) zc = 0;   /* too fragmented for one table */
     }
     const int mode = dev_src ? MODE_NONE : zc ? MODE_ZEROCOPY : MODE_STAGED;
-    int rc = sub_begin(b, &s, kind, fastcrc, after);
+    int rc = sub_begin(b, &s, o);
     if (rc) return rc;
     uint64_t i = 0;
     while (i < n) {
-        struct slot *sl = b->failed ? NULL : slot_open(b, mode, s.kind, s.fastcrc);
-        if (!sl || b->failed) {              /* the device failed meanwhile (slot_open may wait) */
-            if (sl) slot_try_launch(b, sl);  /* an empty slot it opened retires */
-            rc = -ENODEV;
-            break;
-        }
+        struct slot *sl = slot_for(b, mode, s.kind, s.fastcrc);
+        if (!sl) { rc = -ENODEV; break; }
         const uint64_t at = sl->n;
         const uint64_t lo = sl->used;
         const long got = reserve(b, sl, src, i, n, zc);
         if (got < 0) { rc = (int)got; break; }
         if (got == 0) {                      /* nothing fit: close it and take a fresh one */
-            sl->full = 1;
-            b->open = -1;
-            slot_try_launch(b, sl);
+            close_open(b);
             continue;
         }
         const uint64_t m = (uint64_t)got;
@@ -1784,29 +1707,19 @@ static int submit(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, u
          * (a drained c3q step's 6 vectors: ~0.12 ms of copies that no longer
          * sit between the burst and its kernel); appended descriptors are
          * final, slot_prepare copies only what follows */
-        if (dev_src && m >= EARLY_COPY_MIN && sl->n > DESC_DIRECT_MAX && sl->n > sl->copied_n) {
-            const uint64_t c0 = sl->copied_n, cn = sl->n - c0;
-            if (hipMemcpyAsync(sl->d_off + c0, sl->h_off + c0, 8 * cn, hipMemcpyHostToDevice, sl->stream) ||
-                hipMemcpyAsync(sl->d_len + c0, sl->h_len + c0, 4 * cn, hipMemcpyHostToDevice, sl->stream)) {
-                if (!sl->err) sl->err = -EIO;
-            } else {
-                sl->copied_n = sl->n;
-            }
-        }
-        slot_after(b, sl, after);
-        if ((rc = seg_push(sl, (struct seg){s.t, at, m, digests + (size_t)s.dsz * i, on_device}))) {
+        if (dev_src && m >= EARLY_COPY_MIN && sl->n > DESC_DIRECT_MAX && sl->n > sl->copied_n &&
+            desc_copy(sl) && !sl->err)
+            sl->err = -EIO;
+        slot_after(b, sl, o->after);
+        if ((rc = seg_push(b, sl, (struct seg){s.t, at, m, o->digests + (size_t)s.dsz * i, o->on_device}))) {
             sl->err = rc;                    /* its reserved chunks have no segment */
             break;
         }
-        tk_ring_ref(&b->tk, s.t);
         if (mode == MODE_STAGED && hi > lo) {
-            /* copy outside the lock: other submitters may reserve behind us */
-            sl->writers++;
-            pthread_mutex_unlock(&b->mu);
+            write_begin(b, sl);
             gather_range(src, i, m, sl->h_off + at, sl->h_data, lo, hi,
                          sl->kind == MD5HIP_DIGEST_CRC32 ? sl->fastcrc : 0);
-            pthread_mutex_lock(&b->mu);
-            sl->writers--;
+            write_end(b, sl);
         }
         i += m;
         /* the caller waits right away: no linger; the slot goes while fewer
@@ -1818,7 +1731,7 @@ static int submit(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, u
         if (urgent && i >= n) sl->urgent = 1;
         slot_try_launch(b, sl);
     }
-    return sub_end(b, &s, rc, ticket, !async);
+    return sub_end(b, &s, rc, o->ticket, !o->async);
 }
 
 /* A waiter or poller on `ticket` (mu held): if its chunks sit in the open
@@ -1836,20 +1749,16 @@ static void hasten(md5hip_batcher *b, uint64_t ticket)
         }
 }
 
-/* Wait, poll and flush may launch the open slot from the caller's thread
- * (slot_enqueue's device-keyed state: the BALANCED counter, CU counts), so
- * they run on the batcher's device like submit -- a pool waits on a ticket
- * of one device from a thread whose current device is another. */
+/* Wait, poll and flush may launch the open slot from the caller's thread:
+ * batcher_enter. */
 int md5_batch_wait(md5hip_batcher *b, uint64_t ticket)
 {
     if (!b) return -EINVAL;
     if (ticket == 0) return 0;               /* "nothing submitted" */
     struct dev_guard g;
-    if (dev_enter(&g, b->device)) return -ENODEV;
-    pthread_mutex_lock(&b->mu);
+    if (batcher_enter(b, &g)) return -ENODEV;
     const int rc = ticket >= b->tk.hi ? -EINVAL : wait_ticket(b, ticket);
-    pthread_mutex_unlock(&b->mu);
-    dev_leave(&g);
+    batcher_leave(b, &g);
     return rc;
 }
 
@@ -1858,8 +1767,7 @@ int md5_batch_poll(md5hip_batcher *b, uint64_t ticket)
     if (!b) return -EINVAL;
     if (ticket == 0) return 1;
     struct dev_guard g;
-    if (dev_enter(&g, b->device)) return -ENODEV;
-    pthread_mutex_lock(&b->mu);
+    if (batcher_enter(b, &g)) return -ENODEV;
     int rc, err = 0;
     if (ticket >= b->tk.hi) {
         rc = -EINVAL;
@@ -1869,8 +1777,7 @@ int md5_batch_poll(md5hip_batcher *b, uint64_t ticket)
         hasten(b, ticket);                   /* progress without the caller blocking */
         rc = 0;
     }
-    pthread_mutex_unlock(&b->mu);
-    dev_leave(&g);
+    batcher_leave(b, &g);
     return rc;
 }
 
@@ -1878,15 +1785,9 @@ int md5_batch_flush(md5hip_batcher *b)
 {
     if (!b) return -EINVAL;
     struct dev_guard g;
-    if (dev_enter(&g, b->device)) return -ENODEV;
-    pthread_mutex_lock(&b->mu);
-    if (b->open >= 0) {
-        struct slot *o = &b->s[b->open];
-        o->flush = 1;
-        slot_try_launch(b, o);
-    }
-    pthread_mutex_unlock(&b->mu);
-    dev_leave(&g);
+    if (batcher_enter(b, &g)) return -ENODEV;
+    flush_open(b);
+    batcher_leave(b, &g);
     return 0;
 }
 
@@ -1933,11 +1834,9 @@ static int host_pinned(const void *p, uint64_t len)
 /* Fixed-length chunks from one contiguous range (MODE_FIXED, a FIXED
  * source), one slot per slice of it: host memory (one H2D copy per slot, no
  * host gather) or device memory (base_on_device: read in place, no per-chunk
- * descriptor -- md5_batch_submit_device_fixed).  Digests to host memory, or
- * device memory when dig_dev.  after != NULL: the producer's stream, as
- * submit().  ticket NULL = synchronous. */
-static int fixed_submit(md5hip_batcher *b, int kind, uint32_t fastcrc, const struct md5hip_src *fx, uint64_t n,
-                        unsigned char *digests, int dig_dev, const hipStream_t *after, uint64_t *ticket)
+ * descriptor -- md5_batch_submit_device_fixed).  Synchronous when the options
+ * name no ticket. */
+static int fixed_submit(md5hip_batcher *b, const struct md5hip_src *fx, uint64_t n, const struct sub_opt *o)
 {
     const int dev_src = fx->base_on_device;
     const uint32_t len = fx->len;
@@ -1953,18 +1852,12 @@ static int fixed_submit(md5hip_batcher *b, int kind, uint32_t fastcrc, const str
      * the device while it runs (submitters' p90 +2.7 ms beside 128 MiB
      * slices, profiles/r05f/) */
     const int pinned = !dev_src && n && host_pinned(src, (n - 1) * stride + len);
-    int rc = sub_begin(b, &s, kind, fastcrc, after);
+    int rc = sub_begin(b, &s, o);
     if (rc) return rc;
     for (uint64_t i = 0; i < n && !rc; i += per) {
         const uint64_t m = n - i < per ? n - i : per;
-        /* straight from the caller's buffer: a slot of its own (the open
-         * slot keeps coalescing other work) */
-        struct slot *sl = b->failed ? NULL : slot_take(b, MODE_FIXED, s.kind, s.fastcrc);
-        if (!sl || b->failed) {              /* the device failed (slot_take may wait) */
-            if (sl) slot_retire(b, sl, -ENODEV);
-            rc = -ENODEV;
-            break;
-        }
+        struct slot *sl = slot_for(b, MODE_FIXED, s.kind, s.fastcrc);
+        if (!sl) { rc = -ENODEV; break; }
         sl->n = m;
         sl->fx_src = src + i * stride;
         sl->fx_dev = dev_src;
@@ -1972,14 +1865,12 @@ static int fixed_submit(md5hip_batcher *b, int kind, uint32_t fastcrc, const str
         sl->fx_len = len;
         sl->fx_stride = stride;
         sl->full = 1;
-        sl->load = m * ((uint64_t)len + 64);
-        __atomic_store_n(&b->load_bytes, b->load_bytes + sl->load, __ATOMIC_RELAXED);
-        if ((rc = seg_push(sl, (struct seg){s.t, 0, m, digests + (size_t)s.dsz * i, dig_dev}))) {
+        load_add(b, sl, m * ((uint64_t)len + 64));      /* the slot is fresh: load == 0 */
+        if ((rc = seg_push(b, sl, (struct seg){s.t, 0, m, o->digests + (size_t)s.dsz * i, o->on_device}))) {
             slot_retire(b, sl, rc);
             break;
         }
-        tk_ring_ref(&b->tk, s.t);
-        slot_after(b, sl, after);            /* the slot is fresh: err == 0 */
+        slot_after(b, sl, o->after);         /* the slot is fresh: err == 0 */
         if (!dev_src) {
             /* the copy outside the lock, the slot held by this writer: a
              * pageable source through the pinned staging (host_pinned), a
@@ -1987,99 +1878,111 @@ static int fixed_submit(md5hip_batcher *b, int kind, uint32_t fastcrc, const str
              * needs b->mu meanwhile.  Nothing else touches a FIXED slot's
              * stream or staging until its writers are done (slot_try_launch
              * waits for writers == 0). */
-            sl->writers++;
-            pthread_mutex_unlock(&b->mu);
+            write_begin(b, sl);
             const void *from = sl->fx_src;
             if (!pinned) {
                 copy_parallel(sl->h_data, sl->fx_src, sl->fx_bytes);
                 from = sl->h_data;
             }
             const hipError_t ce = hipMemcpyAsync(sl->d_data, from, sl->fx_bytes, hipMemcpyHostToDevice, sl->stream);
-            pthread_mutex_lock(&b->mu);
-            sl->writers--;
+            write_end(b, sl);
             if (!pinned) b->st.bytes_staged += sl->fx_bytes;
             if (ce != hipSuccess && !sl->err) sl->err = -EIO;
             if (ce != hipSuccess && hip_lost(hipStreamQuery(sl->stream))) batcher_fail(b);
         }
         slot_try_launch(b, sl);
     }
-    return sub_end(b, &s, rc, ticket, !ticket);
+    return sub_end(b, &s, rc, o->ticket, !o->ticket);
 }
 
 /* ------------------------------------------------------------------------
  * Entries
  * ------------------------------------------------------------------------ */
-/* What every submit entry does once it has named its source: the argument
- * checks, then the engine the source goes to.  async as submit()'s: non-zero
- * takes a ticket, which is zeroed first (an empty batch is complete at
- * once, and no error leaves a stale ticket). */
-static int enter(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, unsigned char *digests,
-                 int on_device, int async, uint64_t *ticket, int kind, uint32_t fastcrc,
-                 const hipStream_t *after)
+/* What every submit entry does once it has named its source and options:
+ * the argument checks, then the engine the source goes to.  A non-zero
+ * `async` takes a ticket, which is zeroed first (an empty batch is complete
+ * at once, and no error leaves a stale ticket). */
+static int enter(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, const struct sub_opt *o)
 {
-    if (ticket) *ticket = 0;
-    if (!b || (async && !ticket)) return -EINVAL;
+    if (o->ticket) *o->ticket = 0;
+    if (!b || (o->async && !o->ticket)) return -EINVAL;
     if (n == 0) return 0;
-    if (!digests) return -EINVAL;
+    if (!o->digests) return -EINVAL;
     const int rc = md5hip_src_check(src, n);
     if (rc) return rc;
-    return src->kind == MD5HIP_SRC_FIXED
-               ? fixed_submit(b, kind, fastcrc, src, n, digests, on_device, after, ticket)
-               : submit(b, src, n, digests, on_device, async, ticket, kind, fastcrc, after);
+    return src->kind == MD5HIP_SRC_FIXED ? fixed_submit(b, src, n, o) : submit(b, src, n, o);
+}
+
+static struct md5hip_src src_ptrs(const void *const *ptrs, const uint32_t *lens)
+{
+    return (struct md5hip_src){.kind = MD5HIP_SRC_PTRS, .ptrs = ptrs, .lens = lens};
+}
+
+static struct md5hip_src src_iov(const struct md5hip_iov *segs, const uint64_t *seg_first)
+{
+    return (struct md5hip_src){.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+}
+
+static struct md5hip_src src_device(const uint64_t *d_ptrs, const uint32_t *lens)
+{
+    return (struct md5hip_src){.kind = MD5HIP_SRC_DEVICE, .dptrs = d_ptrs, .lens = lens};
 }
 
 int md5_batch_submit(md5hip_batcher *b, const void *const *ptrs, const uint32_t *lens, uint64_t n,
                      unsigned char *digests)
 {
-    const struct md5hip_src src = {.kind = MD5HIP_SRC_PTRS, .ptrs = ptrs, .lens = lens};
-    return enter(b, &src, n, digests, 0, 0, NULL, -1, 0, NULL);
+    const struct md5hip_src src = src_ptrs(ptrs, lens);
+    return enter(b, &src, n, &(struct sub_opt){.digests = digests, .kind = KIND_BATCHER});
 }
 
 int md5_batch_submit_async(md5hip_batcher *b, const void *const *ptrs, const uint32_t *lens,
                            uint64_t n, unsigned char *digests, uint64_t *ticket)
 {
-    const struct md5hip_src src = {.kind = MD5HIP_SRC_PTRS, .ptrs = ptrs, .lens = lens};
-    return enter(b, &src, n, digests, 0, 1, ticket, -1, 0, NULL);
+    const struct md5hip_src src = src_ptrs(ptrs, lens);
+    return enter(b, &src, n, &(struct sub_opt){.digests = digests, .async = 1, .ticket = ticket, .kind = KIND_BATCHER});
 }
 
 int md5_batch_submit_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
                          const uint64_t *seg_first, uint64_t n, unsigned char *digests)
 {
-    const struct md5hip_src src = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
-    return enter(b, &src, n, digests, 0, 0, NULL, -1, 0, NULL);
+    const struct md5hip_src src = src_iov(segs, seg_first);
+    return enter(b, &src, n, &(struct sub_opt){.digests = digests, .kind = KIND_BATCHER});
 }
 
 int md5_batch_submit_iov_async(md5hip_batcher *b, const struct md5hip_iov *segs,
                                const uint64_t *seg_first, uint64_t n, unsigned char *digests,
                                uint64_t *ticket)
 {
-    const struct md5hip_src src = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
-    return enter(b, &src, n, digests, 0, 1, ticket, -1, 0, NULL);
+    const struct md5hip_src src = src_iov(segs, seg_first);
+    return enter(b, &src, n, &(struct sub_opt){.digests = digests, .async = 1, .ticket = ticket, .kind = KIND_BATCHER});
 }
 
 int md5_batch_submit_device_async(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
                                   uint64_t n, unsigned char *digests, int digests_on_device,
                                   uint64_t *ticket)
 {
-    const struct md5hip_src src = {.kind = MD5HIP_SRC_DEVICE, .dptrs = d_ptrs, .lens = lens};
-    return enter(b, &src, n, digests, digests_on_device != 0, 1, ticket, -1, 0, NULL);
+    const struct md5hip_src src = src_device(d_ptrs, lens);
+    return enter(b, &src, n, &(struct sub_opt){.digests = digests, .on_device = digests_on_device != 0,
+                                               .async = 1, .ticket = ticket, .kind = KIND_BATCHER});
 }
 
 int md5_batch_submit_device(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
                             uint64_t n, unsigned char *digests, int digests_on_device)
 {
-    const struct md5hip_src src = {.kind = MD5HIP_SRC_DEVICE, .dptrs = d_ptrs, .lens = lens};
-    return enter(b, &src, n, digests, digests_on_device != 0, 0, NULL, -1, 0, NULL);
+    const struct md5hip_src src = src_device(d_ptrs, lens);
+    return enter(b, &src, n, &(struct sub_opt){.digests = digests, .on_device = digests_on_device != 0,
+                                               .kind = KIND_BATCHER});
 }
 
 int md5_batch_submit_device_after(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
                                   uint64_t n, unsigned char *digests, int digests_on_device,
                                   void *producer_stream, int order, uint64_t *ticket)
 {
-    const struct md5hip_src src = {.kind = MD5HIP_SRC_DEVICE, .dptrs = d_ptrs, .lens = lens};
+    const struct md5hip_src src = src_device(d_ptrs, lens);
     const hipStream_t after = (hipStream_t)producer_stream;
-    return enter(b, &src, n, digests, digests_on_device != 0, ticket != NULL, ticket, -1, 0,
-                 order ? &after : NULL);
+    return enter(b, &src, n, &(struct sub_opt){.digests = digests, .on_device = digests_on_device != 0,
+                                               .async = ticket != NULL, .ticket = ticket, .kind = KIND_BATCHER,
+                                               .after = order ? &after : NULL});
 }
 
 int md5_batch_submit_device_on(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
@@ -2097,15 +2000,16 @@ int md5_batch_submit_device_fixed(md5hip_batcher *b, const void *d_base, uint64_
     const struct md5hip_src src = {.kind = MD5HIP_SRC_FIXED, .base = d_base, .len = len, .stride = stride,
                                    .base_on_device = 1};
     const hipStream_t after = (hipStream_t)producer_stream;
-    return enter(b, &src, n, digests, digests_on_device != 0, ticket != NULL, ticket, -1, 0,
-                 order ? &after : NULL);
+    return enter(b, &src, n, &(struct sub_opt){.digests = digests, .on_device = digests_on_device != 0,
+                                               .async = ticket != NULL, .ticket = ticket, .kind = KIND_BATCHER,
+                                               .after = order ? &after : NULL});
 }
 
 int md5hip_batch_host_fixed(md5hip_batcher *b, const void *h_base, uint64_t n, uint32_t len,
                             uint64_t stride, unsigned char *digests)
 {
     const struct md5hip_src src = {.kind = MD5HIP_SRC_FIXED, .base = h_base, .len = len, .stride = stride};
-    return enter(b, &src, n, digests, 0, 0, NULL, -1, 0, NULL);
+    return enter(b, &src, n, &(struct sub_opt){.digests = digests, .kind = KIND_BATCHER});
 }
 
 /* ------------------------------------------------------------------------
@@ -2123,7 +2027,8 @@ int md5hip_submit_src(md5hip_batcher *b, int kind, uint32_t fastcrc, const struc
 {
     struct md5hip_src part = *src;
     part.first += lo;
-    return enter(b, &part, hi - lo, digests, 0, ticket ? (urgent ? 2 : 1) : 0, ticket, kind, fastcrc, NULL);
+    return enter(b, &part, hi - lo, &(struct sub_opt){.digests = digests, .async = ticket ? (urgent ? 2 : 1) : 0,
+                                                      .ticket = ticket, .kind = kind, .fastcrc = fastcrc});
 }
 
 int md5hip_batcher_ticket_state(md5hip_batcher *b, uint64_t ticket, int *err)
@@ -2136,13 +2041,31 @@ int md5hip_batcher_ticket_state(md5hip_batcher *b, uint64_t ticket, int *err)
     return rc;
 }
 
+/* The digests of `kind` of n page-list chunks, by one synchronous submission
+ * of this call's own kind (the batcher's setting is untouched, so concurrent
+ * users are unaffected), in a fresh array the caller frees: *out, NULL on an
+ * error. */
+static int iov_digests(md5hip_batcher *b, int kind, uint32_t fastcrc, const struct md5hip_iov *segs,
+                       const uint64_t *seg_first, uint64_t n, unsigned char **out)
+{
+    *out = NULL;
+    const struct md5hip_src src = src_iov(segs, seg_first);
+    int rc = md5hip_src_check(&src, n);
+    if (rc) return rc;
+    unsigned char *got = malloc((size_t)md5hip_digest_size(kind) * n);
+    if (!got) return -ENOMEM;
+    rc = submit(b, &src, n, &(struct sub_opt){.digests = got, .kind = kind, .fastcrc = fastcrc});
+    if (rc) free(got);
+    else *out = got;
+    return rc;
+}
+
 /* Batched verify for the cache-read / write-verify sites (blk_io.c:665-704,
  * bc_mgr.c:1464-1492): ok[i] = digest(chunk i) == expected[i]; returns the
  * number of mismatching chunks (>= 0) or -errno.  A mismatch is what
  * dm_verify_block_crc (diskcache.c:3245-3265) reports per block; the caller
  * applies its own EAGAIN / inode-reset policy per flagged block.
- * md5hip_verify_iov_as: with an explicit digest kind for this call only (the
- * batcher's setting is untouched, so concurrent users are unaffected). */
+ * md5hip_verify_iov_as: with an explicit digest kind for this call only. */
 int md5hip_verify_iov_as(md5hip_batcher *b, int kind, uint32_t fastcrc,
                          const struct md5hip_iov *segs, const uint64_t *seg_first, uint64_t n,
                          const void *expected, unsigned char *ok)
@@ -2152,14 +2075,9 @@ int md5hip_verify_iov_as(md5hip_batcher *b, int kind, uint32_t fastcrc,
     if (!expected || !ok) return -EINVAL;
     int rc;
     if ((rc = md5hip_digest_usable(kind, fastcrc))) return rc;
-    const struct md5hip_src src = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
-    rc = md5hip_src_check(&src, n);
-    if (rc) return rc;
-    const uint32_t dsz = md5hip_digest_size(kind);
-    unsigned char *got = malloc((size_t)dsz * n);
-    if (!got) return -ENOMEM;
-    rc = submit(b, &src, n, got, 0, 0, NULL, kind, fastcrc, NULL);
-    if (rc == 0) rc = md5hip_verify_count(got, expected, dsz, n, ok);
+    unsigned char *got;
+    if ((rc = iov_digests(b, kind, fastcrc, segs, seg_first, n, &got))) return rc;
+    rc = md5hip_verify_count(got, expected, md5hip_digest_size(kind), n, ok);
     free(got);
     return rc;
 }
@@ -2176,8 +2094,7 @@ int md5hip_batch_verify_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
 }
 
 /* Verify the stored CRC-32 and produce the MD5 of every chunk in one pass:
- * an MD5_CRC32 submission of this call's own (md5hip_verify_iov_as's
- * mechanism: the batcher's kind is not touched). */
+ * the MD5_CRC32 records of the chunks, then counted. */
 int md5hip_batch_upgrade_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
                              const uint64_t *seg_first, uint64_t n, const uint32_t *want_crc,
                              unsigned char *ok, unsigned char *md5_out)
@@ -2187,12 +2104,9 @@ int md5hip_batch_upgrade_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
     if (rc) return rc;
     if (n == 0) return 0;
     if (!want_crc || !ok || !md5_out) return -EINVAL;
-    const struct md5hip_src src = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
-    if ((rc = md5hip_src_check(&src, n))) return rc;
-    unsigned char *rec = malloc(32 * (size_t)n);
-    if (!rec) return -ENOMEM;
-    rc = submit(b, &src, n, rec, 0, 0, NULL, MD5HIP_DIGEST_MD5_CRC32, 0, NULL);
-    if (rc == 0) rc = md5hip_upgrade_count(rec, want_crc, n, ok, md5_out);
+    unsigned char *rec;
+    if ((rc = iov_digests(b, MD5HIP_DIGEST_MD5_CRC32, 0, segs, seg_first, n, &rec))) return rc;
+    rc = md5hip_upgrade_count(rec, want_crc, n, ok, md5_out);
     free(rec);
     return rc;
 }

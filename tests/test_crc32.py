@@ -280,7 +280,7 @@ def test_gpu_crc_queue_long_blocks_split(cuda):
 def test_gpu_fastcrc_host_blocks_stage_only_windows(cuda, registered):
     """A CRC-32 batcher with a fastcrc window F stages (or maps, zero-copy)
     only the first and last F bytes of each host block over 2F bytes (shorter
-    ones whole; md5_submit.c staged_len): lengths around F and 2F, empty blocks, and page lists cut
+    ones whole; md5_source.h staged_len): lengths around F and 2F, empty blocks, and page lists cut
     inside either window.  Every CRC equals crc32.c's blk_make_crc rule
     (blk_io.c:408-424), and the bytes staged are the windows' (stats)."""
     F = 128
@@ -340,7 +340,7 @@ def test_gpu_fragmented_chunks_at_the_zero_copy_table_edge(cuda, kind):
     """Chunks of ~4,096 one-byte segments of registered memory (a 1 MiB
     slice's zero-copy table holds 4,096 entries): a chunk goes zero-copy only
     if its pieces fit an empty slot, else it is staged, and either way its
-    digest is right (md5_submit.c zc_pieces)."""
+    digest is right (md5_source.h zc_pieces)."""
     F = 100
     buf = gen.xorshift_array(2 * 4200 + 64, seed=4096)
     m.register_host(buf)
