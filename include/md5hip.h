@@ -33,7 +33,9 @@ extern "C" {
 /* ABI 5 + md5crc32: the one-pass MD5 + CRC-32 digest kind
  * (MD5HIP_DIGEST_MD5_CRC32, struct md5hip_md5crc32), md5crc32hip_fixed /
  * md5crc32hip_desc and md5hip_batch_upgrade_iov / md5hip_pool_upgrade_iov
- * (appended; the version number is unchanged, a caller finds them by symbol).
+ * (appended; the version number is unchanged, a caller finds them by symbol);
+ * then, the same way, its small-batch kernel: enum md5crc32hip_variant,
+ * md5crc32hip_fixed_variant / md5crc32hip_desc_variant and md5crc32hip_plan.
  * ABI 5 (round 6): md5hip_order_stable_scratch / md5hip_order_device_stable
  * (appended; the batcher's large slots use them); md5hip_batch_host_fixed
  * reads a source in place only if it is pinned over its whole range.
@@ -204,6 +206,44 @@ int md5crc32hip_fixed(const void *d_base, uint64_t n, uint32_t len, uint64_t str
 int md5crc32hip_desc(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
                      const uint32_t *d_order, uint64_t n, struct md5hip_md5crc32 *d_out,
                      void *stream);
+
+/* Kernels of the one-pass kind for md5crc32hip_*_variant (appended; ABI 5). */
+enum md5crc32hip_variant {
+    MD5CRC32HIP_AUTO = 0,     /* md5crc32hip_plan's choice where the entry knows the lengths
+                                 (the fixed one); XDMA16 where it does not (the desc one) */
+    MD5CRC32HIP_XDMA16 = 1,   /* one lane per chunk runs both chains over LDS-DMA images, 12
+                                 waves per CU: what md5crc32hip_fixed / _desc launch */
+    MD5CRC32HIP_FEDSPLIT = 2, /* small batches: one launch whose first ceil(n/64) workgroups
+                                 run the MD5s as fed pairs (MD5HIP_DESC_FED) and whose other
+                                 workgroups cut each CRC-32 across a wave (CRC32HIP_SPLIT);
+                                 any n, alignment and stride */
+    MD5CRC32HIP_NUM_VARIANTS = 3
+};
+/* AUTO picks FEDSPLIT from this mean chunk length on.  It started at 2048,
+ * the split CRC's own crossover; measured under this kind FEDSPLIT is still
+ * well ahead at 1 KiB (1,024 x 1 KiB: 15 us against XDMA16's 25) and level at
+ * 512 B (15 against 15), where its fixed cost -- 64 KiB of tables per
+ * workgroup, the split's tree of shifts -- is XDMA16's whole launch
+ * (profiles/dual_small/ab.json). */
+#define MD5CRC32HIP_FEDSPLIT_MIN_LEN 1024u
+/* The variant AUTO takes for n chunks of mean_len bytes (host only):
+ * FEDSPLIT for at most one 64-chunk group per CU of the current device,
+ * mean_len >= MD5CRC32HIP_FEDSPLIT_MIN_LEN and n <= CUs x mean_len / 256
+ * (many short chunks are bound by the CRC role's fixed work per chunk: 2,048
+ * chunks at 2 KiB, every one-group-per-CU batch from 16 KiB on); else
+ * XDMA16 (n = 0 included). */
+int md5crc32hip_plan(uint64_t n, uint64_t mean_len);
+/* md5crc32hip_fixed / _desc with the kernel named; an unknown variant is
+ * -EINVAL.  The plain entries launch XDMA16 for every batch.  AUTO of the
+ * fixed entry takes FEDSPLIT only from a 16-B aligned base and stride below
+ * 2^31/64 (what MD5HIP_AUTO asks of its fed pairs); AUTO of the desc entry,
+ * whose lengths are on the device, is XDMA16: a caller that knows them
+ * passes md5crc32hip_plan's answer (the batcher does). */
+int md5crc32hip_fixed_variant(const void *d_base, uint64_t n, uint32_t len, uint64_t stride,
+                              struct md5hip_md5crc32 *d_out, void *stream, int variant);
+int md5crc32hip_desc_variant(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+                             const uint32_t *d_order, uint64_t n, struct md5hip_md5crc32 *d_out,
+                             void *stream, int variant);
 
 /*
  * Host helper: order[] = indices of lens[] sorted by MD5 block count,

@@ -163,6 +163,9 @@ def lib():
         "md5crc32hip_desc": (i, [vp, vp, vp, vp, u64, vp, vp]),
         "md5hip_batch_upgrade_iov": (i, [vp, vp, vp, u64, vp, vp, vp]),
         "md5hip_pool_upgrade_iov": (i, [vp, vp, vp, u64, vp, vp, vp]),
+        "md5crc32hip_plan": (i, [u64, u64]),
+        "md5crc32hip_fixed_variant": (i, [vp, u64, u32, u64, vp, vp, i]),
+        "md5crc32hip_desc_variant": (i, [vp, vp, vp, vp, u64, vp, vp, i]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -201,7 +204,8 @@ EXPORTS = ["MD5Init", "MD5Update", "MD5Final", "nc_MD5Init", "nc_MD5Update", "nc
            "md5_batch_submit_device_after", "md5hip_plan_desc_at", "md5hip_batcher_set_chain",
            "md5hip_batcher_health", "md5hip_batcher_inject_fault", "md5hip_pool_get_health",
            "md5hip_pool_device_health", "md5hip_pool_inject_fault", "md5_batch_submit_device_fixed",
-           "md5crc32hip_fixed", "md5crc32hip_desc", "md5hip_batch_upgrade_iov", "md5hip_pool_upgrade_iov"]
+           "md5crc32hip_fixed", "md5crc32hip_desc", "md5hip_batch_upgrade_iov", "md5hip_pool_upgrade_iov",
+           "md5crc32hip_plan", "md5crc32hip_fixed_variant", "md5crc32hip_desc_variant"]
 
 
 def check(fn, rc):

@@ -143,8 +143,19 @@ static inline int md5hip_digest_valid(int kind, uint32_t fastcrc)
 extern __typeof__(md5crc32hip_fixed) md5crc32hip_fixed __attribute__((weak));
 extern __typeof__(md5crc32hip_desc) md5crc32hip_desc __attribute__((weak));
 static inline int md5hip_md5crc32_present(void) { return &md5crc32hip_fixed && &md5crc32hip_desc; }
+/* So are the entries that name the kernel, and the planner's choice between
+ * them: a build with the plain launchers alone (tests/c/fake_dual.c) calls
+ * those for every batch. */
+extern __typeof__(md5crc32hip_fixed_variant) md5crc32hip_fixed_variant __attribute__((weak));
+extern __typeof__(md5crc32hip_desc_variant) md5crc32hip_desc_variant __attribute__((weak));
+extern __typeof__(md5crc32hip_plan) md5crc32hip_plan __attribute__((weak));
+static inline int md5hip_md5crc32_variants_present(void)
+{
+    return &md5crc32hip_fixed_variant && &md5crc32hip_desc_variant && &md5crc32hip_plan;
+}
 #else
 static inline int md5hip_md5crc32_present(void) { return 1; }
+static inline int md5hip_md5crc32_variants_present(void) { return 1; }
 #endif
 /* 0, -EINVAL (no such kind / window) or -ENOSYS (MD5_CRC32 without its launchers) */
 static inline int md5hip_digest_usable(int kind, uint32_t fastcrc)

@@ -1267,7 +1267,10 @@ crc32_desc_xdma16(const uint8_t* __restrict__ base, const uint64_t* __restrict__
 
 // MD5 + CRC-32 in one pass (Md5Crc32Hasher, 32-B records) in XDMA16's frame:
 // the 64 KiB tables beside twelve 8 KiB images, one 768-thread workgroup per
-// CU, 3 waves per SIMD.  A throughput kind: no small-batch variants.
+// CU, 3 waves per SIMD.  The throughput shape: a batch of at most one 64-chunk
+// group per CU leaves one live wave per workgroup, which runs both chains of
+// its lanes back to back; such batches go to md5crc32_fedsplit (below), as
+// md5crc32hip_plan decides.
 __global__ void __launch_bounds__(768)
 md5crc32_fixed_xdma16(const uint8_t* __restrict__ base, uint64_t n, uint32_t len, uint64_t stride,
                       Md5Crc32Record* __restrict__ out) {
@@ -1496,6 +1499,69 @@ crc32_split(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
     else
       crc = split_crc_msg(h, m, L, lane);
     if (lane == 63u) out[c] = crc;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// MD5 + CRC-32 of small batches ("fedsplit"): the two small-batch kernels in
+// one launch, a role per workgroup.  md5crc32_*_xdma16 keeps one lane per
+// chunk for both chains; with at most one 64-chunk group per CU that is a lone
+// wave per workgroup running 64 MD5 chains and 64 CRC chains back to back,
+// the CRC lookups hidden under nobody's MD5 steps.  Here
+//   workgroups [0, g), g = ceil(n / 64): md5_desc_fed's body -- a fed pair per
+//     group (fed_long_group), LANE's lane-direct body on wave 0 for a group
+//     with a chunk start off the 16-B grid or no chunk of two whole blocks --
+//     storing bytes 0..15 of record c (index 2c of the records as uint4);
+//   workgroups [g, gridDim.x): crc32_split's body -- one wave per chunk
+//     (split_crc_msg), grid-stride over all n chunks -- lane 63 storing bytes
+//     16..31 of record c as (crc, 0, 0, 0).
+// So every byte of a record is written once, and no 16 bytes by both roles.
+// The role is uniform over the workgroup and taken before any barrier: the
+// bare s_barrier hand-over of a fed pair counts on exactly its two waves, so
+// a CRC wave cannot share a workgroup with one (it would hold every
+// hand-over).  One 64 KiB LDS array -- the fed pair's two tables in its first
+// half, the CRC role's 16 table copies in all of it -- so a CU holds two
+// workgroups, and with g <= CUs and at most CUs CRC workgroups the whole grid
+// is resident at once; the chains have the low indices and are placed first.
+// (Registers agree: the fed pair's 163 VGPRs beside the split's 93 AGPRs of
+// shift constants are one wave per SIMD, four per CU.)
+// ---------------------------------------------------------------------------
+template <bool kImplicit>
+__global__ void __launch_bounds__(128)
+md5crc32_fedsplit(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
+                  const uint32_t* __restrict__ lens, const uint32_t* __restrict__ order, uint64_t n,
+                  uint64_t stride, uint32_t flen, Md5Crc32Record* __restrict__ out) {
+  static_assert(2 * kFedTable <= (uint32_t)Crc32PermHasher::kLdsBytes, "the fed tables lie in the CRC tables' array");
+  __shared__ __attribute__((aligned(16))) uint8_t lds[Crc32PermHasher::kLdsBytes];
+  const auto src = chunk_source<kImplicit>(offs, lens, order, stride, flen);
+  uint4* rec = reinterpret_cast<uint4*>(out);          // record c = rec[2c] (md5), rec[2c + 1] (crc)
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t g = (n + 63) / 64;
+  if (blockIdx.x < g) {                                // the MD5 role
+    const GroupLane L = group_lane(src, base, n, (uint64_t)blockIdx.x * 64u);
+    const uint32_t bmax = wave_max(L.nfull);
+    const bool unaligned = L.any_unaligned();
+    if (bmax >= kFedMinBlocks && !unaligned) {         // wave-uniform, the same in both waves
+      fed_long_group(base, rec, lds, wave == 1, L.nfull, bmax, L.off, L.len, 2 * L.c, L.live);
+      return;
+    }
+    if (wave != 0 || !L.live) return;
+    Md5Hasher<true> h;
+    typename Md5Hasher<true>::State st = h.init();
+    lane_range<Md5Hasher<true>, 8>(h, st, L.chunk, L.len);
+    h.store(rec, 2 * L.c, st);
+    return;
+  }
+  Crc32PermHasher h;                                   // the CRC role
+  h.setup(lds);                                        // all threads, before any exit
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wpb = blockDim.x >> 6;
+  const uint64_t nb = gridDim.x - g;                   // CRC workgroups
+  for (uint64_t q = (blockIdx.x - g) * wpb + wave; q < n; q += nb * wpb) {
+    const uint64_t c = src.index(q);
+    const uint8_t* m = chunk_at<decltype(src)::kAbs>(base, src.off(c));
+    const uint32_t crc = split_crc_msg(h, m, src.len(c), lane);
+    if (lane == 63u) rec[2 * c + 1] = make_uint4(crc, 0u, 0u, 0u);
   }
 }
 

@@ -563,4 +563,50 @@ int md5hip_order_device_stable(const uint32_t* d_lens, uint64_t n, uint32_t kmax
   return launched();
 }
 
+// The one-pass kind with the kernel named.  (At the end of the file, so that
+// md5crc32_fedsplit is the code object's last kernel and every other one
+// keeps its place.)  FEDSPLIT: ceil(n/64) MD5 workgroups, then CRC workgroups
+// of two waves, one chunk per wave, at most one per CU.
+static uint64_t fedsplit_grid(uint64_t n) {
+  const uint64_t half = (n + 1) / 2, cap = (uint64_t)md5hip_cu_count();
+  return (n + 63) / 64 + (half < cap ? half : cap);
+}
+
+static int fedsplit_launch(const void* base, const uint64_t* offs, const uint32_t* lens,
+                           const uint32_t* order, uint64_t n, uint64_t stride, uint32_t flen,
+                           struct md5hip_md5crc32* d_out, void* stream) {
+  return launch(offs ? md5crc32_fedsplit<false> : md5crc32_fedsplit<true>, fedsplit_grid(n), 128, 0, stream,
+                base, offs, lens, order, n, stride, flen, reinterpret_cast<Md5Crc32Record*>(d_out));
+}
+
+static bool dual_variant_known(int v) { return v >= MD5CRC32HIP_AUTO && v < MD5CRC32HIP_NUM_VARIANTS; }
+
+int md5crc32hip_fixed_variant(const void* d_base, uint64_t n, uint32_t len, uint64_t stride,
+                              struct md5hip_md5crc32* d_out, void* stream, int variant) {
+  if (n == 0) return 0;
+  if (int e = ready(d_base && d_out && len <= stride && aligned(d_out, 16) && dual_variant_known(variant),
+                    fedsplit_grid(n)))
+    return e;
+  if (variant == MD5CRC32HIP_AUTO)
+    variant = aligned(d_base, 16) && (stride & 15u) == 0 && stride < (1ull << 31) / 64
+                  ? md5crc32hip_plan(n, len)
+                  : MD5CRC32HIP_XDMA16;
+  if (variant == MD5CRC32HIP_FEDSPLIT)
+    return fedsplit_launch(d_base, nullptr, nullptr, nullptr, n, stride, len, d_out, stream);
+  return md5crc32hip_fixed(d_base, n, len, stride, d_out, stream);
+}
+
+int md5crc32hip_desc_variant(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
+                             const uint32_t* d_order, uint64_t n, struct md5hip_md5crc32* d_out,
+                             void* stream, int variant) {
+  if (n == 0) return 0;
+  if (int e = ready(d_base && d_offsets && d_lens && d_out && aligned(d_out, 16) && dual_variant_known(variant),
+                    fedsplit_grid(n)))
+    return e;
+  // AUTO: the lengths are on the device, so the caller names FEDSPLIT
+  if (variant == MD5CRC32HIP_FEDSPLIT)
+    return fedsplit_launch(d_base, d_offsets, d_lens, d_order, n, 0, 0, d_out, stream);
+  return md5crc32hip_desc(d_base, d_offsets, d_lens, d_order, n, d_out, stream);
+}
+
 }  // extern "C"

@@ -9,6 +9,7 @@
 
 #include <thread>
 
+#define MD5HIP_DEFINES_MD5CRC32   // md5crc32hip_plan is defined here, not weakly referenced
 #include "md5_internal.h"
 
 namespace {
@@ -107,6 +108,29 @@ int md5hip_crc_desc_choice(uint64_t n, uint64_t mean_len) {
 // (with fastcrc the batcher passes 2n windows of fastcrc bytes; windows under
 // the launchers' kCrcSplitMinWindow keep the window kernels whatever the
 // variant says)
+
+// The one-pass MD5 + CRC-32 kind (md5hip.h).  XDMA16 keeps one lane per chunk
+// for both chains, ~20 ns per byte of chunk whatever the count: a batch of at
+// most one 64-chunk group per CU is a lone wave per workgroup running them
+// back to back (325 us at 16 KiB, 45 us at 2 KiB, 25 us at 1 KiB).  FEDSPLIT
+// gives such a batch the two small-batch kernels in one launch: the MD5s as
+// fed pairs (135 us at 16 KiB) beside two CRC waves per CU, each taking a
+// chunk in ~5.5 us of mostly fixed work (the split's tree of shifts), so the
+// CRC role lasts ceil(n / (2 x CUs)) x 5.5 us and bounds the launch once the
+// chunks are many and short: 16,384 x 1 KiB ran 170 us against XDMA16's 26,
+// 1,024 x 1 KiB 15 against 25.  Hence two bounds beside the fed pairs' own:
+// chunks of >= MD5CRC32HIP_FEDSPLIT_MIN_LEN bytes (below, FEDSPLIT's ~15 us
+// floor is XDMA16's whole launch), and at most CUs x mean_len / 256 chunks --
+// the CRC role then lasts about half of XDMA16's time (2,048 chunks at
+// 2 KiB: 25 us against 46; every fed-pair batch from 16 KiB on).  profiles/dual_small/ab.json,
+// DESIGN.md §5.8.
+constexpr uint64_t kDualLenPerChunkCu = 256;
+int md5crc32hip_plan(uint64_t n, uint64_t mean_len) {
+  return n && md5hip_fed_fits((n + 63) / 64) && mean_len >= MD5CRC32HIP_FEDSPLIT_MIN_LEN &&
+                 n * kDualLenPerChunkCu <= cus() * mean_len
+             ? MD5CRC32HIP_FEDSPLIT
+             : MD5CRC32HIP_XDMA16;
+}
 
 int md5hip_plan_order(const uint32_t* lens, uint64_t n, uint32_t* order) {
   if (n == 0) return 0;

@@ -498,6 +498,25 @@ static int enqueue_bytes(md5hip_batcher *b, struct slot *sl)
     return 0;
 }
 
+/* The MD5_CRC32 launches: the kernel is md5crc32hip_plan's (small vectors
+ * run as fed pairs beside split CRCs); a build that has the plain launchers
+ * only (md5_internal.h) calls those. */
+static int dual_fixed(const void *src, uint64_t n, uint32_t len, uint64_t stride, struct md5hip_md5crc32 *dst,
+                      void *stream)
+{
+    return md5hip_md5crc32_variants_present()
+               ? md5crc32hip_fixed_variant(src, n, len, stride, dst, stream, MD5CRC32HIP_AUTO)
+               : md5crc32hip_fixed(src, n, len, stride, dst, stream);
+}
+
+static int dual_desc(const void *base, const uint64_t *off, const uint32_t *len, const uint32_t *ord, uint64_t n,
+                     uint64_t mean_len, struct md5hip_md5crc32 *dst, void *stream)
+{
+    return md5hip_md5crc32_variants_present()
+               ? md5crc32hip_desc_variant(base, off, len, ord, n, dst, stream, md5crc32hip_plan(n, mean_len))
+               : md5crc32hip_desc(base, off, len, ord, n, dst, stream);
+}
+
 /* The hash kernel, digests to `dst`, and `kdone` behind it. */
 static int enqueue_kernel(struct slot *sl, unsigned char *dst)
 {
@@ -516,7 +535,7 @@ static int enqueue_kernel(struct slot *sl, unsigned char *dst)
         rc = sl->kind == MD5HIP_DIGEST_CRC32
                  ? crc32hip_fixed(src, n, sl->fx_len, sl->fx_stride, sl->fastcrc, (uint32_t *)dst, sl->stream)
              : sl->kind == MD5HIP_DIGEST_MD5_CRC32
-                 ? md5crc32hip_fixed(src, n, sl->fx_len, sl->fx_stride, (struct md5hip_md5crc32 *)dst, sl->stream)
+                 ? dual_fixed(src, n, sl->fx_len, sl->fx_stride, (struct md5hip_md5crc32 *)dst, sl->stream)
                  : md5hip_digest_fixed(src, n, sl->fx_len, sl->fx_stride, dst, sl->stream);
     } else {
         const uint32_t *ord = sl->use_order ? sl->d_ord : NULL;
@@ -528,8 +547,9 @@ static int enqueue_kernel(struct slot *sl, unsigned char *dst)
                                          md5hip_crc_desc_choice(sl->fastcrc ? 2 * n : n,
                                                                 sl->fastcrc ? sl->fastcrc
                                                                             : sl->load / n - 64))
-             : sl->kind == MD5HIP_DIGEST_MD5_CRC32      /* one frame for every batch: the plan's order only */
-                 ? md5crc32hip_desc(sl->d_data, doff, dlen, ord, n, (struct md5hip_md5crc32 *)dst, sl->stream)
+             : sl->kind == MD5HIP_DIGEST_MD5_CRC32      /* the plan's order; the kernel by the mean length */
+                 ? dual_desc(sl->d_data, doff, dlen, ord, n, sl->load / n - 64, (struct md5hip_md5crc32 *)dst,
+                             sl->stream)
                  : md5hip_digest_desc_variant(sl->d_data, doff, dlen, ord, n,
                                               dst, sl->stream, sl->plan_var);
     }

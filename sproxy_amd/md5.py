@@ -237,10 +237,28 @@ def crc32_desc(base, offsets, lens, order=None, fastcrc: int = 0, out=None, stre
     return out
 
 
-def md5crc32_fixed(data, n: int = None, length: int = None, stride: int = None, out=None, stream=None):
+MD5CRC32_VARIANTS = {"auto": 0, "xdma16": 1, "fedsplit": 2}   # enum md5crc32hip_variant
+MD5CRC32_FEDSPLIT_MIN_LEN = 1024                             # MD5CRC32HIP_FEDSPLIT_MIN_LEN
+
+
+def md5crc32_plan(n: int, mean_len: int) -> str:
+    """Name (MD5CRC32_VARIANTS key) of the kernel "auto" takes for n chunks of
+    mean_len bytes (md5crc32hip_plan; host only)."""
+    v = lib().md5crc32hip_plan(n, mean_len)
+    return {x: k for k, x in MD5CRC32_VARIANTS.items()}[v]
+
+
+def _dual_variant(variant):
+    return MD5CRC32_VARIANTS[variant] if isinstance(variant, str) else variant
+
+
+def md5crc32_fixed(data, n: int = None, length: int = None, stride: int = None, out=None, stream=None,
+                   variant=None):
     """record[i] = MD5 and CRC-32 of chunk i from one read of its bytes
     (struct md5hip_md5crc32): uint8 [n, 32] on device -- md5 at 0..15, the
-    CRC little-endian at 16..19, zeros at 20..31 (split_records)."""
+    CRC little-endian at 16..19, zeros at 20..31 (split_records).  variant:
+    None = the plain entry (XDMA16 for every batch), else a MD5CRC32_VARIANTS
+    name or value."""
     _need_cuda(data, "data")
     if n is None or length is None:
         if data.dim() != 2:
@@ -252,14 +270,21 @@ def md5crc32_fixed(data, n: int = None, length: int = None, stride: int = None, 
     if out is None:
         out = torch.empty((n, 32), dtype=torch.uint8, device=data.device)
     _need_cuda(out, "out")
-    check("md5crc32hip_fixed",
-          lib().md5crc32hip_fixed(data.data_ptr(), n, length, stride, out.data_ptr(), _stream(stream)))
+    if variant is None:
+        check("md5crc32hip_fixed",
+              lib().md5crc32hip_fixed(data.data_ptr(), n, length, stride, out.data_ptr(), _stream(stream)))
+    else:
+        check("md5crc32hip_fixed_variant",
+              lib().md5crc32hip_fixed_variant(data.data_ptr(), n, length, stride, out.data_ptr(),
+                                              _stream(stream), _dual_variant(variant)))
     return out
 
 
-def md5crc32_desc(base, offsets, lens, order=None, out=None, stream=None):
+def md5crc32_desc(base, offsets, lens, order=None, out=None, stream=None, variant=None):
     """record[i] = MD5 and CRC-32 of base_bytes[offsets[i] : offsets[i] + lens[i]]
-    (as md5crc32_fixed): uint8 [n, 32] on device."""
+    (as md5crc32_fixed): uint8 [n, 32] on device.  The lengths are on the
+    device, so "auto" is xdma16 here: name "fedsplit" for a small batch
+    (md5crc32_plan)."""
     _need_cuda(base, "base")
     _need_cuda(offsets, "offsets")
     _need_cuda(lens, "lens")
@@ -275,10 +300,12 @@ def md5crc32_desc(base, offsets, lens, order=None, out=None, stream=None):
     if out is None:
         out = torch.empty((n, 32), dtype=torch.uint8, device=base.device)
     _need_cuda(out, "out")
-    check("md5crc32hip_desc",
-          lib().md5crc32hip_desc(base.data_ptr(), offsets.data_ptr(), lens.data_ptr(),
-                                 order.data_ptr() if order is not None else None, n, out.data_ptr(),
-                                 _stream(stream)))
+    args = (base.data_ptr(), offsets.data_ptr(), lens.data_ptr(),
+            order.data_ptr() if order is not None else None, n, out.data_ptr(), _stream(stream))
+    if variant is None:
+        check("md5crc32hip_desc", lib().md5crc32hip_desc(*args))
+    else:
+        check("md5crc32hip_desc_variant", lib().md5crc32hip_desc_variant(*args, _dual_variant(variant)))
     return out
 
 
@@ -824,7 +851,8 @@ def pool_plan(lens, nparts: int) -> np.ndarray:
 
 __all__ = ["init_ctx", "update_ctx", "final_ctx", "MD5Context", "MD5Init", "MD5Update", "MD5Final", "MD5_DIGEST_SIZE", "MD5HipError", "arena_empty",
            "plan_desc", "plan_desc_at",
-           "md5", "digest_fixed", "digest_desc", "crc32_fixed", "crc32_desc", "md5crc32_fixed", "md5crc32_desc",
+           "md5", "digest_fixed", "digest_desc", "crc32_fixed", "crc32_desc", "md5crc32_fixed", "md5crc32_desc", "md5crc32_plan",
+           "MD5CRC32_VARIANTS", "MD5CRC32_FEDSPLIT_MIN_LEN",
            "split_records", "plan_order", "fill_synthetic", "Batcher",
            "Pool", "Queue", "pool_plan", "CRC_VARIANTS", "DESC_VARIANTS",
            "register_host", "unregister_host",
