@@ -1523,8 +1523,9 @@ crc32_split(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
 // half, the CRC role's 16 table copies in all of it -- so a CU holds two
 // workgroups, and with g <= CUs and at most CUs CRC workgroups the whole grid
 // is resident at once; the chains have the low indices and are placed first.
-// (Registers agree: the fed pair's 163 VGPRs beside the split's 93 AGPRs of
-// shift constants are one wave per SIMD, four per CU.)
+// (Registers allow it: 163 VGPRs, the split's shift constants among them, and
+// no AGPRs are three waves per SIMD; the LDS's two workgroups of two waves
+// are one per SIMD, four per CU.)
 // ---------------------------------------------------------------------------
 template <bool kImplicit>
 __global__ void __launch_bounds__(128)

@@ -223,10 +223,12 @@ int md5hip_digest_fixed_variant(const void* d_base, uint64_t n, uint32_t len, ui
   if (n == 0) return 0;
   const bool known = variant == MD5HIP_AUTO || variant == MD5HIP_DIRECT2 || variant == MD5HIP_XDMA1NT;
   const uint64_t grid = (n + kBlock - 1) / kBlock, g = (n + 63) / 64;
-  if (int e = ready(d_base && d_digests && len <= stride && aligned(d_digests, 16) && known, grid))
+  // chunk starts off the 16-B grid launch g workgroups, the others `grid`
+  const bool off_grid = !aligned(d_base, 16) || (stride & 15u) != 0;
+  if (int e = ready(d_base && d_digests && len <= stride && aligned(d_digests, 16) && known, off_grid ? g : grid))
     return e;
   uint4* out = (uint4*)d_digests;
-  if (!aligned(d_base, 16) || (stride & 15u) != 0)
+  if (off_grid)
     // chunk starts not 16-B aligned: descriptor kernel with implicit offsets
     return launch(md5_desc<true>, g, kDescBlock, 0, stream, d_base, nullptr, nullptr, nullptr, n, stride,
                   len, out);
