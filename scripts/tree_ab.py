@@ -14,6 +14,8 @@ Workloads (--set bench: the first three; --set site: the rest):
   latency   scripts/latency_probe.py: median us per synchronous device call
   submit    scripts/probes/submit_cost.py: the C call's cost per 79 K-chunk
             device submission (reserve_device)
+  poollat   scripts/pool_latency_probe.py: median us per synchronous submit
+            through a batcher, a pool over one device and one over four
 
 Per figure: every tree's values and median, the old-vs-old2 gap, new against
 old (positive = new worse), and whether that is within twice the gap.  Stops
@@ -74,6 +76,11 @@ def submit_figs(rec, _):
             for mode, runs in rec["us_median"].items()}
 
 
+def poollat_figs(rec, _):
+    return {f"poollat.{shape}.{k}.median_us": (v[k]["median_us"], -1)
+            for shape, v in rec.items() for k in ("batcher", "pool1", "pool4")}
+
+
 def point_figs(rec, _):
     assert rec.get("mismatches", 1) == 0, "asio_scale: a digest differs from the oracle"
     key = f"asio.{rec['mode']}.{rec['target']}.T{rec['threads']}"
@@ -93,6 +100,7 @@ def workloads(secs, points=()):
                  asio_figs),
         "latency": ("site", [PY, "scripts/latency_probe.py", "--iters", "200"], latency_figs),
         "submit": ("site", [PY, "scripts/probes/submit_cost.py", "--bursts", "8"], submit_figs),
+        "poollat": ("site", [PY, "scripts/pool_latency_probe.py", "--iters", "200", "--secs", "0.5"], poollat_figs),
     }
 
 

@@ -21,12 +21,18 @@
  * counters, the multi-part ticket table) and is never held across a batcher
  * call that waits for the device.  No thread is created per call.
  *
- * Failed devices (md5hip_batcher_health): never routed to.  A part that
- * finds its device failed before the device took it (-ENODEV) goes to
- * another; a synchronous submission or part whose launch failed with its
- * device is resubmitted on a healthy one from the caller's buffers (still
- * valid: the call has not returned); an asynchronous ticket keeps its -EIO
- * (or -ENODEV if it was still coalescing).
+ * A submission is one or more parts (struct pool_part): a contiguous chunk
+ * range, its weight and, once placed, its device and batcher ticket.  One
+ * routed whole is the single part [0, n); a split one is the k parts that
+ * plan_next cuts, all claimed by one route call before the first is placed.
+ *
+ * Failed devices (md5hip_batcher_health): never routed to.  part_place puts
+ * a part on its device and, while that device has failed and so refuses it
+ * (-ENODEV before it took the part), on another.  part_settle waits for a
+ * synchronous caller's part and, while its launch failed with its device,
+ * places it again from the caller's buffers (still valid: the call has not
+ * returned).  An asynchronous ticket keeps its -EIO (or -ENODEV if it was
+ * still coalescing).  Each move off a failed device is one failover.
  *
  * Tickets: a submission routed whole is (batcher ticket << 6) | device; a
  * split one is bit 63 | id, its parts kept in `mt` (ascending ids) until all
@@ -40,20 +46,23 @@
 
 #include "../../include/md5hip.h"
 #include "md5_internal.h"
+#include "md5_tickets.h"
 
 #define POOL_MAX_DEV 64
 #define MT_BIT (1ull << 63)
 #define FAILED_MAX (1u << 16)
 
-struct mt_part {
-    uint32_t dev;
-    uint64_t t;
+struct pool_part {
+    uint64_t lo, hi;                  /* chunks [lo, hi) of the submission */
+    uint64_t w;                       /* their weight */
+    uint32_t dev;                     /* once routed: the device, w claimed on it until placed */
+    uint64_t t;                       /* once placed: the batcher's ticket */
 };
 
 struct mt_entry {                      /* one split submission */
     uint64_t id;
     uint32_t nparts;
-    struct mt_part part[];
+    struct pool_part part[];
 };
 
 struct md5hip_pool {
@@ -70,34 +79,74 @@ struct md5hip_pool {
     /* split tickets still running, ascending ids; [mt_lo, mt_lo + mt_n) of a ring */
     struct mt_entry **mt;
     uint64_t mt_cap, mt_lo, mt_n, mt_next;
-    /* split tickets that completed with an error: (id, err), ascending */
-    uint64_t *failed_id;
-    int *failed_err;
-    uint64_t nfailed, capfailed;
+    struct tk_failed_list failed;     /* split tickets that completed with an error */
 };
 
 /* Per-chunk weight for the byte balance: payload plus a fixed cost per chunk
  * (one descriptor and one padding block), so empty chunks still spread. */
 static inline uint64_t chunk_weight(uint64_t len) { return len + 64; }
 
+/* weight of chunks [0, n) */
+static inline __attribute__((always_inline)) uint64_t src_total(const struct md5hip_src *s, uint64_t n)
+{
+    if (s->kind == MD5HIP_SRC_FIXED) return n * chunk_weight(s->len);
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; i++) total += chunk_weight(md5hip_src_len(s, i));
+    return total;
+}
+
+/* The one walk that cuts chunks [0, n) of weight `total` into k contiguous
+ * byte-balanced parts: part g starts at the first chunk whose prefix weight
+ * reaches g*total/k (a chunk that straddles the target goes to the side that
+ * holds more of it).  A FIXED source has the closed form: equal counts. */
+struct plan_walk {
+    const struct md5hip_src *s;
+    uint64_t n, total;
+    uint32_t k, g;                    /* g: the part plan_next yields next */
+    uint64_t i, acc;                  /* its first chunk, and the weight before that */
+};
+
+static inline __attribute__((always_inline)) struct pool_part plan_next(struct plan_walk *c)
+{
+    struct pool_part q = {.lo = c->i, .hi = c->n, .w = c->total - c->acc};
+    const uint32_t g = ++c->g;
+    if (g >= c->k) return q;                            /* the last part takes the rest */
+    if (c->s->kind == MD5HIP_SRC_FIXED) {
+        q.hi = c->n * g / c->k;
+        q.w = (q.hi - q.lo) * chunk_weight(c->s->len);
+    } else {
+        const unsigned __int128 target = (unsigned __int128)c->total * g / c->k;
+        uint64_t i = c->i, acc = c->acc;
+        while (i < c->n) {
+            const uint64_t w = chunk_weight(md5hip_src_len(c->s, i));
+            if (acc + w / 2 >= target) break;
+            acc += w;
+            i++;
+        }
+        q.hi = i;
+        q.w = acc - c->acc;
+    }
+    c->i = q.hi;
+    c->acc += q.w;
+    return q;
+}
+
+/* Inlined into its two callers, where the source kind is a constant: the
+ * ABI entry's walk over a plain length array then costs what it did when it
+ * was written out for one. */
+static inline __attribute__((always_inline)) void plan_firsts(const struct md5hip_src *s, uint64_t n,
+                                                              uint32_t nparts, uint64_t *first)
+{
+    struct plan_walk c = {.s = s, .n = n, .total = src_total(s, n), .k = nparts};
+    for (uint32_t g = 0; g < nparts; g++) first[g] = plan_next(&c).lo;
+    first[nparts] = n;
+}
+
 int md5hip_pool_plan(const uint32_t *lens, uint64_t n, uint32_t nparts, uint64_t *first)
 {
     if (!first || nparts == 0) return -EINVAL;
-    if (n && !lens) {                                   /* equal counts */
-        for (uint32_t g = 0; g <= nparts; g++) first[g] = n * g / nparts;
-        return 0;
-    }
-    uint64_t total = 0;
-    for (uint64_t i = 0; i < n; i++) total += chunk_weight(lens[i]);
-    /* part g starts at the first chunk whose prefix weight reaches g*total/G */
-    first[0] = 0;
-    uint64_t i = 0, acc = 0;
-    for (uint32_t g = 1; g < nparts; g++) {
-        const unsigned __int128 target = (unsigned __int128)total * g / nparts;
-        while (i < n && acc + chunk_weight(lens[i]) / 2 < target) acc += chunk_weight(lens[i++]);
-        first[g] = i;
-    }
-    first[nparts] = n;
+    if (lens) plan_firsts(&(const struct md5hip_src){.kind = MD5HIP_SRC_PTRS, .lens = lens}, n, nparts, first);
+    else plan_firsts(&(const struct md5hip_src){.kind = MD5HIP_SRC_FIXED}, n, nparts, first);   /* equal counts */
     return 0;
 }
 
@@ -107,8 +156,7 @@ void md5hip_pool_destroy(md5hip_pool *p)
     for (uint32_t g = 0; g < p->ndev; g++) md5hip_batcher_destroy(p->b[g]);
     for (uint64_t k = 0; k < p->mt_n; k++) free(p->mt[(p->mt_lo + k) % p->mt_cap]);
     free(p->mt);
-    free(p->failed_id);
-    free(p->failed_err);
+    free(p->failed.e);
     pthread_mutex_destroy(&p->mu);
     free(p);
 }
@@ -124,6 +172,7 @@ int md5hip_pool_create(const int *devices, uint32_t ndev, uint64_t slice_bytes, 
     pthread_mutex_init(&p->mu, NULL);
     p->kind = MD5HIP_DIGEST_MD5;
     p->mt_next = 1;
+    p->failed.max = FAILED_MAX;
     for (uint32_t g = 0; g < ndev; g++) {
         int rc = md5hip_batcher_create(devices[g], slice_bytes, nslots, &p->b[g]);
         if (rc) {
@@ -221,10 +270,11 @@ static uint64_t dev_load(md5hip_pool *p, uint32_t g)
 
 static int dev_ok(md5hip_pool *p, uint32_t g) { return md5hip_batcher_health(p->b[g]) == 0; }
 
-/* The k least-loaded healthy devices (ties from a rotating start), their
- * weight w claimed on each; into sel[0..k).  Returns how many were chosen:
- * fewer than k when fewer devices are healthy (0: every device failed). */
-static uint32_t route(md5hip_pool *p, uint32_t k, const uint64_t *w, uint32_t *sel)
+/* The k least-loaded healthy devices (ties from a rotating start) for
+ * part[0..k): part j's device, its weight claimed there.  Returns how many
+ * were chosen: fewer than k when fewer devices are healthy (0: every device
+ * failed). */
+static uint32_t route(md5hip_pool *p, uint32_t k, struct pool_part *part)
 {
     const uint32_t G = p->ndev;
     const uint32_t r0 = __atomic_fetch_add(&p->rr, 1, __ATOMIC_RELAXED);
@@ -242,55 +292,50 @@ static uint32_t route(md5hip_pool *p, uint32_t k, const uint64_t *w, uint32_t *s
         }
         if (best == G) return j;
         used[best] = 1;
-        sel[j] = best;
-        __atomic_fetch_add(&p->claim[best], w[j], __ATOMIC_RELAXED);
+        part[j].dev = best;
+        __atomic_fetch_add(&p->claim[best], part[j].w, __ATOMIC_RELAXED);
     }
     return k;
 }
 
-static void unclaim(md5hip_pool *p, uint32_t g, uint64_t w)
+static void unclaim(md5hip_pool *p, const struct pool_part *q)
 {
-    __atomic_fetch_sub(&p->claim[g], w, __ATOMIC_RELAXED);
+    __atomic_fetch_sub(&p->claim[q->dev], q->w, __ATOMIC_RELAXED);
 }
 
 /* ------------------------------------------------------------------------
- * Split-ticket table (p->mu held)
+ * Tickets
  * ------------------------------------------------------------------------ */
-static void failed_add(md5hip_pool *p, uint64_t id, int err)
+/* wait for (block = 1) or poll (block = 0) ticket t of device g's batcher:
+ * 1 done and *err its error, 0 running, -EINVAL no such ticket */
+static int ticket_step(md5hip_pool *p, uint32_t g, uint64_t t, int block, int *err)
 {
-    if (p->nfailed == p->capfailed) {
-        if (p->capfailed >= FAILED_MAX) {                 /* keep the newest half */
-            const uint64_t keep = p->nfailed / 2;
-            memmove(p->failed_id, p->failed_id + p->nfailed - keep, keep * sizeof *p->failed_id);
-            memmove(p->failed_err, p->failed_err + p->nfailed - keep, keep * sizeof *p->failed_err);
-            p->nfailed = keep;
-        } else {
-            const uint64_t nc = p->capfailed ? 2 * p->capfailed : 64;
-            uint64_t *fi = realloc(p->failed_id, nc * sizeof *fi);
-            if (fi) p->failed_id = fi;
-            int *fe = realloc(p->failed_err, nc * sizeof *fe);
-            if (fe) p->failed_err = fe;
-            if (!fi || !fe) return;
-            p->capfailed = nc;
-        }
-    }
-    p->failed_id[p->nfailed] = id;
-    p->failed_err[p->nfailed] = err;
-    p->nfailed++;
+    const int r = block ? md5_batch_wait(p->b[g], t) : md5_batch_poll(p->b[g], t);
+    *err = 0;
+    if (r == -EINVAL) return -EINVAL;
+    if (!block && r >= 0) return r;
+    *err = r;
+    return 1;
 }
 
-static int failed_find(const md5hip_pool *p, uint64_t id)
+/* ticket_step over parts that this pool placed: 1 every part done, 0 some
+ * running (each has been hastened); the first part error into *err if it
+ * holds none yet */
+static int parts_step(md5hip_pool *p, const struct pool_part *part, uint32_t np, int block, int *err)
 {
-    uint64_t a = 0, z = p->nfailed;
-    while (a < z) {
-        const uint64_t mid = (a + z) / 2;
-        if (p->failed_id[mid] < id) a = mid + 1;
-        else z = mid;
+    int done = 1;
+    for (uint32_t j = 0; j < np; j++) {
+        int e;
+        const int s = ticket_step(p, part[j].dev, part[j].t, block, &e);
+        if (s < 0) e = s;
+        else if (s == 0) done = 0;
+        if (e && !*err) *err = e;
     }
-    return a < p->nfailed && p->failed_id[a] == id ? p->failed_err[a] : 0;
+    return done;
 }
 
-/* 1 = every part done (*err = the first part error), 0 = running */
+/* 1 = every part done (*err = the first part error), 0 = running; launches
+ * and waits for nothing (p->mu held) */
 static int mt_state(md5hip_pool *p, const struct mt_entry *e, int *err)
 {
     *err = 0;
@@ -304,21 +349,22 @@ static int mt_state(md5hip_pool *p, const struct mt_entry *e, int *err)
     return 1;
 }
 
-/* Drop completed entries from the low end (they are looked up by failed_find
- * from then on). */
+/* Drop completed entries from the low end (their errors are looked up in
+ * p->failed from then on); p->mu held. */
 static void mt_reap(md5hip_pool *p)
 {
     while (p->mt_n) {
         struct mt_entry *e = p->mt[p->mt_lo % p->mt_cap];
         int err;
         if (!mt_state(p, e, &err)) break;
-        if (err) failed_add(p, e->id, err);
+        if (err) tk_failed_add(&p->failed, e->id, err);
         free(e);
         p->mt_lo++;
         p->mt_n--;
     }
 }
 
+/* p->mu held */
 static int mt_push(md5hip_pool *p, struct mt_entry *e)
 {
     if (p->mt_n == p->mt_cap) {
@@ -336,7 +382,8 @@ static int mt_push(md5hip_pool *p, struct mt_entry *e)
     return 0;
 }
 
-/* the live entry with this id, or NULL (completed and dropped, or unknown) */
+/* the live entry with this id, or NULL (completed and dropped, or unknown);
+ * p->mu held */
 static struct mt_entry *mt_find(md5hip_pool *p, uint64_t id)
 {
     uint64_t a = 0, z = p->mt_n;
@@ -352,185 +399,6 @@ static struct mt_entry *mt_find(md5hip_pool *p, uint64_t id)
     return NULL;
 }
 
-/* ------------------------------------------------------------------------
- * Submission
- * ------------------------------------------------------------------------ */
-/* chunks [lo, hi) of `s` to device g's batcher, asynchronously; urgent =
- * the caller waits right away (launch at once, as a synchronous call) */
-static int part_submit(md5hip_pool *p, uint32_t g, int kind, uint32_t fastcrc,
-                       const struct md5hip_src *s, uint64_t lo, uint64_t hi, unsigned char *digests,
-                       uint64_t *ticket, int urgent)
-{
-    return md5hip_submit_src(p->b[g], kind, fastcrc, s, lo, hi, digests, ticket, urgent);
-}
-
-static uint64_t src_weight(const struct md5hip_src *s, uint64_t i)
-{
-    return chunk_weight(md5hip_src_len(s, i));
-}
-
-static void count_failover(md5hip_pool *p)
-{
-    pthread_mutex_lock(&p->mu);
-    p->st_failovers++;
-    pthread_mutex_unlock(&p->mu);
-}
-
-/* Chunks [lo, hi) whole to one healthy device (weight w): *g, *t its device
- * and ticket.  sync: waited here, and resubmitted elsewhere while the launch
- * failed because its device did (the caller's buffers are still valid).
- * Either way a device that failed before taking the chunks (-ENODEV) is
- * left for another.  -ENODEV once no device is healthy. */
-static int submit_range(md5hip_pool *p, int kind, uint32_t fastcrc, const struct md5hip_src *s,
-                        uint64_t lo, uint64_t hi, uint64_t w, unsigned char *digests, int sync,
-                        uint32_t *g_out, uint64_t *t_out)
-{
-    for (;;) {
-        uint32_t g;
-        if (!route(p, 1, &w, &g)) return -ENODEV;     /* every device failed */
-        /* asynchronous even for a synchronous caller, so the claim ends as
-         * soon as the batcher holds the chunks (its own load counts them) */
-        uint64_t t = 0;
-        int rc = part_submit(p, g, kind, fastcrc, s, lo, hi, digests, &t, sync);
-        unclaim(p, g, w);
-        if (rc == 0 && sync) rc = md5_batch_wait(p->b[g], t);
-        if ((rc == -ENODEV || (sync && rc == -EIO)) && !dev_ok(p, g)) {
-            count_failover(p);                        /* moved off the failed device */
-            continue;
-        }
-        *g_out = g;
-        *t_out = t;
-        return rc;
-    }
-}
-
-/* n > 0 valid chunks, *ticket zeroed (pool_enter); ticket NULL =
- * synchronous; kind < 0 = the pool's current digest kind */
-static int pool_submit(md5hip_pool *p, const struct md5hip_src *s, uint64_t n, unsigned char *digests,
-                       uint64_t *ticket, int kind, uint32_t fastcrc)
-{
-    pthread_mutex_lock(&p->mu);
-    if (kind < 0) {
-        kind = p->kind;
-        fastcrc = p->fastcrc;
-    }
-    uint64_t split = p->split_bytes;
-    p->st.submissions++;
-    pthread_mutex_unlock(&p->mu);
-    if (split == 0) split = md5hip_batcher_slice(p->b[0]);
-    const uint32_t dsz = md5hip_digest_size(kind);
-    const int sync = ticket == NULL;
-    uint64_t total = 0;
-    if (s->kind == MD5HIP_SRC_FIXED) {
-        total = n * chunk_weight(s->len);
-    } else {
-        for (uint64_t i = 0; i < n; i++) total += src_weight(s, i);
-    }
-    uint32_t healthy = 0;
-    for (uint32_t g = 0; g < p->ndev; g++) healthy += dev_ok(p, g);
-    if (healthy == 0) return -ENODEV;
-    uint32_t k = 1;
-    if (total > split && healthy > 1) {
-        const uint64_t want = (total + split - 1) / split;
-        k = want < healthy ? (uint32_t)want : healthy;
-        if (k > n) k = (uint32_t)n;
-    }
-    if (k == 1) {                                     /* the common case: whole */
-        uint32_t g = 0;
-        uint64_t t = 0;
-        const int rc = submit_range(p, kind, fastcrc, s, 0, n, total, digests, sync, &g, &t);
-        pthread_mutex_lock(&p->mu);
-        p->st.routed_whole++;
-        p->st.parts++;
-        pthread_mutex_unlock(&p->mu);
-        if (ticket && rc == 0 && t) *ticket = (t << 6) | g;
-        return rc;
-    }
-    /* split: contiguous byte-balanced ranges over the k least-loaded devices */
-    uint64_t first[POOL_MAX_DEV + 1], w[POOL_MAX_DEV];
-    if (s->kind == MD5HIP_SRC_FIXED) {
-        md5hip_pool_plan(NULL, n, k, first);
-    } else {
-        uint32_t *lens = malloc(4 * n);
-        if (!lens) return -ENOMEM;
-        for (uint64_t i = 0; i < n; i++) {
-            const uint64_t L = src_weight(s, i) - 64;
-            lens[i] = L > 0xffffffffull ? 0xffffffffu : (uint32_t)L;   /* the batcher rejects it */
-        }
-        md5hip_pool_plan(lens, n, k, first);
-        free(lens);
-    }
-    for (uint32_t j = 0; j < k; j++) {
-        w[j] = 0;
-        if (s->kind == MD5HIP_SRC_FIXED) w[j] = (first[j + 1] - first[j]) * chunk_weight(s->len);
-        else for (uint64_t i = first[j]; i < first[j + 1]; i++) w[j] += src_weight(s, i);
-    }
-    uint32_t sel[POOL_MAX_DEV];
-    const uint32_t got = route(p, k, w, sel);         /* < k: a device failed since the count */
-    struct mt_entry *e = malloc(sizeof *e + k * sizeof(struct mt_part));
-    int rc = e ? 0 : -ENOMEM;
-    uint32_t np = 0;
-    uint32_t pj[POOL_MAX_DEV];                        /* part index of each submitted part */
-    for (uint32_t j = 0; j < k; j++) {
-        if (rc == 0 && first[j + 1] > first[j]) {
-            uint64_t t = 0;
-            uint32_t g = j < got ? sel[j] : 0;
-            int r = j < got ? part_submit(p, g, kind, fastcrc, s, first[j], first[j + 1],
-                                          digests + (size_t)dsz * first[j], &t, sync)
-                            : -ENODEV;
-            if (r == -ENODEV && (j >= got || !dev_ok(p, g))) {
-                if (j < got) count_failover(p);
-                /* its device failed before taking the part: any healthy one
-                 * (submitted asynchronously like the others; waited below) */
-                r = submit_range(p, kind, fastcrc, s, first[j], first[j + 1], w[j],
-                                 digests + (size_t)dsz * first[j], 0, &g, &t);
-            }
-            rc = r;
-            if (rc == 0 && t) {
-                pj[np] = j;
-                e->part[np++] = (struct mt_part){g, t};
-            }
-        }
-        if (j < got) unclaim(p, sel[j], w[j]);
-    }
-    pthread_mutex_lock(&p->mu);
-    p->st.split++;
-    p->st.parts += np;
-    pthread_mutex_unlock(&p->mu);
-    if (!e) return rc;
-    e->nparts = np;
-    if (rc || sync) {
-        /* synchronous, or a part failed: the submitted parts finish before
-         * the caller may reuse its buffers.  Synchronously, a part whose
-         * launch failed with its device goes again on a healthy one. */
-        for (uint32_t q = 0; q < np; q++) {
-            int r = md5_batch_wait(p->b[e->part[q].dev], e->part[q].t);
-            if (sync && rc == 0 && (r == -EIO || r == -ENODEV) && !dev_ok(p, e->part[q].dev)) {
-                const uint32_t j = pj[q];
-                uint32_t g;
-                uint64_t t;
-                count_failover(p);
-                r = submit_range(p, kind, fastcrc, s, first[j], first[j + 1], w[j],
-                                 digests + (size_t)dsz * first[j], 1, &g, &t);
-            }
-            if (r && !rc) rc = r;
-        }
-        free(e);
-        return rc;
-    }
-    pthread_mutex_lock(&p->mu);
-    mt_reap(p);
-    e->id = p->mt_next++;
-    rc = mt_push(p, e);
-    if (rc == 0) *ticket = MT_BIT | e->id;
-    pthread_mutex_unlock(&p->mu);
-    if (rc) {                                         /* no table space: finish it here */
-        for (uint32_t j = 0; j < np; j++) (void)md5_batch_wait(p->b[e->part[j].dev], e->part[j].t);
-        free(e);
-    }
-    return rc;
-}
-
 /* wait (block = 1) or poll (block = 0) on a pool ticket: 1 done / 0 running
  * and *err its error, or -EINVAL */
 static int pool_ticket(md5hip_pool *p, uint64_t ticket, int block, int *err)
@@ -539,42 +407,24 @@ static int pool_ticket(md5hip_pool *p, uint64_t ticket, int block, int *err)
     if (ticket == 0) return 1;
     if (!(ticket & MT_BIT)) {
         const uint32_t g = (uint32_t)(ticket & 63u);
-        if (g >= p->ndev) return -EINVAL;
-        const int r = block ? md5_batch_wait(p->b[g], ticket >> 6) : md5_batch_poll(p->b[g], ticket >> 6);
-        if (r == -EINVAL) return -EINVAL;
-        if (block) { *err = r; return 1; }
-        if (r < 0) { *err = r; return 1; }
-        return r;                                     /* 1 done, 0 running */
+        return g < p->ndev ? ticket_step(p, g, ticket >> 6, block, err) : -EINVAL;
     }
     const uint64_t id = ticket & ~MT_BIT;
+    struct pool_part parts[POOL_MAX_DEV];
+    uint32_t np = 0;
     pthread_mutex_lock(&p->mu);
-    if (id == 0 || id >= p->mt_next) {
-        pthread_mutex_unlock(&p->mu);
-        return -EINVAL;
+    const int known = id != 0 && id < p->mt_next;
+    const struct mt_entry *e = known ? mt_find(p, id) : NULL;
+    if (e) {
+        np = e->nparts;
+        memcpy(parts, e->part, np * sizeof *parts);
+    } else if (known) {
+        *err = tk_failed_find(&p->failed, id);        /* completed and dropped */
     }
-    struct mt_entry *e = mt_find(p, id);
-    if (!e) {                                         /* completed and dropped */
-        *err = failed_find(p, id);
-        pthread_mutex_unlock(&p->mu);
-        return 1;
-    }
-    struct mt_part parts[POOL_MAX_DEV];
-    const uint32_t np = e->nparts;
-    memcpy(parts, e->part, np * sizeof *parts);
     pthread_mutex_unlock(&p->mu);
-    /* the batcher calls below may block: p->mu is not held */
-    int done = 1;
-    for (uint32_t j = 0; j < np; j++) {
-        const int r = block ? md5_batch_wait(p->b[parts[j].dev], parts[j].t)
-                            : md5_batch_poll(p->b[parts[j].dev], parts[j].t);
-        if (block) {
-            if (r && !*err) *err = r;
-        } else if (r < 0) {
-            if (!*err) *err = r;
-        } else if (r == 0) {
-            done = 0;                                 /* keep polling: every part is hastened */
-        }
-    }
+    if (!e) return known ? 1 : -EINVAL;
+    /* the batcher calls may block: p->mu is not held */
+    const int done = parts_step(p, parts, np, block, err);
     if (done) {
         pthread_mutex_lock(&p->mu);
         mt_reap(p);
@@ -598,6 +448,190 @@ int md5hip_pool_poll(md5hip_pool *p, uint64_t ticket)
     const int r = pool_ticket(p, ticket, 0, &err);
     if (r < 0) return r;
     return r == 1 && err ? err : r;
+}
+
+/* ------------------------------------------------------------------------
+ * Submission
+ * ------------------------------------------------------------------------ */
+struct pool_sub {                      /* what every part of one submission shares */
+    md5hip_pool *p;
+    const struct md5hip_src *s;
+    unsigned char *digests;
+    int kind;
+    uint32_t fastcrc;
+    int sync;                          /* the caller has no ticket: it waits in the call */
+};
+
+/* Opens the submission: the pool's digest kind unless the caller named one
+ * (kind >= 0); returns the split threshold in bytes. */
+static uint64_t sub_open(struct pool_sub *u, int kind, uint32_t fastcrc)
+{
+    md5hip_pool *p = u->p;
+    pthread_mutex_lock(&p->mu);
+    u->kind = kind < 0 ? p->kind : kind;
+    u->fastcrc = kind < 0 ? p->fastcrc : fastcrc;
+    const uint64_t split = p->split_bytes;
+    p->st.submissions++;
+    pthread_mutex_unlock(&p->mu);
+    return split ? split : md5hip_batcher_slice(p->b[0]);
+}
+
+/* parts to cut n chunks of weight `total` into: 1 = whole (the common
+ * case), 0 = no device is healthy */
+static uint32_t part_count(md5hip_pool *p, uint64_t n, uint64_t total, uint64_t split)
+{
+    uint32_t healthy = 0;
+    for (uint32_t g = 0; g < p->ndev; g++) healthy += dev_ok(p, g);
+    if (total <= split || healthy <= 1) return healthy != 0;
+    const uint64_t want = (total + split - 1) / split;
+    const uint64_t k = want < healthy ? want : healthy;
+    return (uint32_t)(k < n ? k : n);
+}
+
+static void count_failover(md5hip_pool *p)
+{
+    pthread_mutex_lock(&p->mu);
+    p->st_failovers++;
+    pthread_mutex_unlock(&p->mu);
+}
+
+static void count_routed(md5hip_pool *p, int split, uint32_t parts)
+{
+    pthread_mutex_lock(&p->mu);
+    if (split) p->st.split++;
+    else p->st.routed_whole++;
+    p->st.parts += parts;
+    pthread_mutex_unlock(&p->mu);
+}
+
+/* Places part q: on the device already claimed for it (claimed, by the
+ * split's route), else on one routed here.  The batcher takes it
+ * asynchronously even for a synchronous caller, so the claim ends with the
+ * submit attempt (the batcher's own load counts the chunks from then on);
+ * urgent for a synchronous caller, who waits right away.  While the device
+ * refuses the part because it has failed, the part moves to another: one
+ * failover each.  -ENODEV once no device is healthy. */
+static int part_place(const struct pool_sub *u, struct pool_part *q, int claimed)
+{
+    md5hip_pool *p = u->p;
+    for (;; claimed = 0) {
+        if (!claimed && !route(p, 1, q)) return -ENODEV;
+        q->t = 0;
+        const int rc = md5hip_submit_src(p->b[q->dev], u->kind, u->fastcrc, u->s, q->lo, q->hi,
+                                         u->digests + (size_t)md5hip_digest_size(u->kind) * q->lo, &q->t, u->sync);
+        unclaim(p, q);
+        if (rc != -ENODEV || dev_ok(p, q->dev)) return rc;
+        count_failover(p);
+    }
+}
+
+static int part_wait(md5hip_pool *p, const struct pool_part *q)
+{
+    int err = 0;
+    parts_step(p, q, 1, 1, &err);
+    return err;
+}
+
+/* Settles placed part q for a synchronous caller: waits for it and, while
+ * its launch failed because its device did, places it again (one failover)
+ * from the caller's buffers and waits again. */
+static int part_settle(const struct pool_sub *u, struct pool_part *q)
+{
+    for (;;) {
+        int rc = part_wait(u->p, q);
+        if ((rc != -EIO && rc != -ENODEV) || dev_ok(u->p, q->dev)) return rc;
+        count_failover(u->p);
+        if ((rc = part_place(u, q, 0))) return rc;
+    }
+}
+
+/* The placed parts finish before the caller may reuse its buffers: settled
+ * for a synchronous caller while no part has failed for good (rc, the error
+ * so far), else only waited for.  Returns the first error. */
+static int parts_finish(const struct pool_sub *u, struct pool_part *part, uint32_t np, int rc)
+{
+    for (uint32_t j = 0; j < np; j++) {
+        const int r = u->sync && rc == 0 ? part_settle(u, &part[j]) : part_wait(u->p, &part[j]);
+        if (r && !rc) rc = r;
+    }
+    return rc;
+}
+
+static int submit_whole(const struct pool_sub *u, uint64_t n, uint64_t total, uint64_t *ticket)
+{
+    struct pool_part q = {.lo = 0, .hi = n, .w = total};
+    int rc = part_place(u, &q, 0);
+    if (rc == 0 && u->sync) rc = part_settle(u, &q);
+    count_routed(u->p, 0, 1);
+    if (ticket && rc == 0 && q.t) *ticket = (q.t << 6) | q.dev;
+    return rc;
+}
+
+/* Places part[0..k), of which route claimed a device for the first `got`,
+ * and moves the placed ones to the front: their count into *np.  A part for
+ * which no device was left (a device failed since part_count) goes to any
+ * healthy one.  After one part's error no further part is placed. */
+static int parts_place(const struct pool_sub *u, struct pool_part *part, uint32_t k, uint32_t got, uint32_t *np)
+{
+    int rc = 0;
+    *np = 0;
+    for (uint32_t j = 0; j < k; j++) {
+        struct pool_part *q = &part[j];
+        if (rc || q->hi == q->lo) {
+            if (j < got) unclaim(u->p, q);
+            continue;
+        }
+        rc = part_place(u, q, j < got);
+        if (rc == 0 && q->t) part[(*np)++] = *q;
+    }
+    return rc;
+}
+
+/* Hands out the split ticket of entry e, whose parts run; without table
+ * space they finish here.  Owns e. */
+static int mt_publish(const struct pool_sub *u, struct mt_entry *e, uint64_t *ticket)
+{
+    md5hip_pool *p = u->p;
+    pthread_mutex_lock(&p->mu);
+    mt_reap(p);
+    e->id = p->mt_next++;
+    const int rc = mt_push(p, e);
+    if (rc == 0) *ticket = MT_BIT | e->id;
+    pthread_mutex_unlock(&p->mu);
+    if (rc) {
+        parts_finish(u, e->part, e->nparts, rc);
+        free(e);
+    }
+    return rc;
+}
+
+/* contiguous byte-balanced ranges over the k least-loaded devices */
+static int submit_split(const struct pool_sub *u, uint64_t n, uint64_t total, uint32_t k, uint64_t *ticket)
+{
+    struct mt_entry *e = malloc(sizeof *e + k * sizeof *e->part);
+    if (!e) return -ENOMEM;
+    struct plan_walk c = {.s = u->s, .n = n, .total = total, .k = k};
+    for (uint32_t j = 0; j < k; j++) e->part[j] = plan_next(&c);
+    const uint32_t got = route(u->p, k, e->part);     /* every claim before the first part is placed */
+    int rc = parts_place(u, e->part, k, got, &e->nparts);
+    count_routed(u->p, 1, e->nparts);
+    if (rc == 0 && !u->sync) return mt_publish(u, e, ticket);
+    rc = parts_finish(u, e->part, e->nparts, rc);
+    free(e);
+    return rc;
+}
+
+/* n > 0 valid chunks, *ticket zeroed (pool_enter); ticket NULL =
+ * synchronous; kind < 0 = the pool's current digest kind */
+static int pool_submit(md5hip_pool *p, const struct md5hip_src *s, uint64_t n, unsigned char *digests,
+                       uint64_t *ticket, int kind, uint32_t fastcrc)
+{
+    struct pool_sub u = {.p = p, .s = s, .digests = digests, .sync = ticket == NULL};
+    const uint64_t split = sub_open(&u, kind, fastcrc);
+    const uint64_t total = src_total(s, n);
+    const uint32_t k = part_count(p, n, total, split);
+    if (k == 0) return -ENODEV;
+    return k == 1 ? submit_whole(&u, n, total, ticket) : submit_split(&u, n, total, k, ticket);
 }
 
 /* ------------------------------------------------------------------------

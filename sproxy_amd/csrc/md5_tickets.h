@@ -6,8 +6,9 @@
  * power-of-two ring: a count of outstanding references (the submission
  * itself, plus one per slot holding its chunks) and the ticket's first error.
  * When the oldest ids reach zero references the ring's low end advances past
- * them.  A ticket that leaves the ring with an error keeps it in `failed`, a
- * sorted list (ids leave in increasing order, so appending keeps it sorted):
+ * them.  A ticket that leaves the ring with an error keeps it in `failed`
+ * (tk_failed_list, which the pool's split tickets use too; ids leave in
+ * increasing order, so appending keeps it sorted):
  * a wait or poll on an old ticket reports that ticket's own error, never
  * another ticket's, and 0 for every ticket that completed cleanly.
  *
@@ -20,22 +21,61 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-/* failed tickets kept for lookup; past this many the oldest half is dropped
- * (a caller that waits on a ticket millions of failures old reads 0) */
-#define TK_FAILED_MAX (1u << 20)
-
+/* Tickets that completed with an error, ascending ids (appended in that
+ * order), for lookup by id.  Past `max` entries the oldest half is dropped:
+ * a caller that waits on a ticket that many failures old reads 0.  Zeroed =
+ * empty; the owner sets `max` and frees `e`. */
 struct tk_failed {
     uint64_t id;
     int err;
 };
+
+struct tk_failed_list {
+    struct tk_failed *e;
+    uint64_t n, cap, max;
+};
+
+static inline void tk_failed_add(struct tk_failed_list *f, uint64_t id, int err)
+{
+    if (f->n == f->cap) {
+        if (f->cap >= f->max) {                       /* drop the oldest half */
+            const uint64_t keep = f->n / 2;
+            for (uint64_t k = 0; k < keep; k++) f->e[k] = f->e[f->n - keep + k];
+            f->n = keep;
+        } else {
+            const uint64_t nc = f->cap ? 2 * f->cap : 64;
+            struct tk_failed *e = (struct tk_failed *)realloc(f->e, nc * sizeof *e);
+            if (!e) return;                           /* no memory: this error reads as 0 later */
+            f->e = e;
+            f->cap = nc;
+        }
+    }
+    f->e[f->n].id = id;
+    f->e[f->n].err = err;
+    f->n++;
+}
+
+/* the error kept for `id`, 0 if none */
+static inline int tk_failed_find(const struct tk_failed_list *f, uint64_t id)
+{
+    uint64_t a = 0, b = f->n;
+    while (a < b) {
+        const uint64_t mid = (a + b) / 2;
+        if (f->e[mid].id < id) a = mid + 1;
+        else b = mid;
+    }
+    return a < f->n && f->e[a].id == id ? f->e[a].err : 0;
+}
+
+/* the batcher's cap on its failed list */
+#define TK_FAILED_MAX (1u << 20)
 
 struct tk_ring {
     uint64_t lo, hi;          /* live ids [lo, hi) */
     uint64_t cap;             /* ring size, a power of two */
     uint32_t *pending;        /* references per live id */
     int *err;                 /* first error per live id */
-    struct tk_failed *failed; /* ids < lo that completed with an error, ascending */
-    uint64_t nfailed, capfailed;
+    struct tk_failed_list failed; /* ids < lo that completed with an error */
 };
 
 static inline int tk_ring_grow(struct tk_ring *r)
@@ -63,8 +103,9 @@ static inline int tk_ring_init(struct tk_ring *r, uint64_t first)
     r->cap = 0;
     r->pending = NULL;
     r->err = NULL;
-    r->failed = NULL;
-    r->nfailed = r->capfailed = 0;
+    r->failed.e = NULL;
+    r->failed.n = r->failed.cap = 0;
+    r->failed.max = TK_FAILED_MAX;
     return tk_ring_grow(r);
 }
 
@@ -72,10 +113,10 @@ static inline void tk_ring_free(struct tk_ring *r)
 {
     free(r->pending);
     free(r->err);
-    free(r->failed);
+    free(r->failed.e);
     r->pending = NULL;
     r->err = NULL;
-    r->failed = NULL;
+    r->failed.e = NULL;
 }
 
 /* a new ticket holding one reference (the submission in progress) */
@@ -98,26 +139,6 @@ static inline void tk_ring_ref(struct tk_ring *r, uint64_t t)
     if (t >= r->lo && t < r->hi) r->pending[t & (r->cap - 1)]++;
 }
 
-static inline void tk_ring_remember(struct tk_ring *r, uint64_t id, int err)
-{
-    if (r->nfailed == r->capfailed) {
-        if (r->capfailed >= TK_FAILED_MAX) {          /* drop the oldest half */
-            const uint64_t keep = r->nfailed / 2;
-            for (uint64_t k = 0; k < keep; k++) r->failed[k] = r->failed[r->nfailed - keep + k];
-            r->nfailed = keep;
-        } else {
-            const uint64_t nc = r->capfailed ? 2 * r->capfailed : 64;
-            struct tk_failed *f = (struct tk_failed *)realloc(r->failed, nc * sizeof *f);
-            if (!f) return;                           /* no memory: this error reads as 0 later */
-            r->failed = f;
-            r->capfailed = nc;
-        }
-    }
-    r->failed[r->nfailed].id = id;
-    r->failed[r->nfailed].err = err;
-    r->nfailed++;
-}
-
 /* drop one reference of ticket t, recording err as its error if it is the
  * first; retire the completed ids at the ring's low end */
 static inline void tk_ring_put(struct tk_ring *r, uint64_t t, int err)
@@ -128,7 +149,7 @@ static inline void tk_ring_put(struct tk_ring *r, uint64_t t, int err)
     if (r->pending[k]) r->pending[k]--;
     while (r->lo < r->hi && r->pending[r->lo & (r->cap - 1)] == 0) {
         const int e = r->err[r->lo & (r->cap - 1)];
-        if (e) tk_ring_remember(r, r->lo, e);
+        if (e) tk_failed_add(&r->failed, r->lo, e);
         r->lo++;
     }
 }
@@ -137,13 +158,7 @@ static inline void tk_ring_put(struct tk_ring *r, uint64_t t, int err)
 static inline int tk_ring_done(const struct tk_ring *r, uint64_t t, int *err)
 {
     if (t < r->lo) {
-        uint64_t a = 0, b = r->nfailed;
-        while (a < b) {
-            const uint64_t mid = (a + b) / 2;
-            if (r->failed[mid].id < t) a = mid + 1;
-            else b = mid;
-        }
-        *err = a < r->nfailed && r->failed[a].id == t ? r->failed[a].err : 0;
+        *err = tk_failed_find(&r->failed, t);
         return 1;
     }
     *err = r->err[t & (r->cap - 1)];

@@ -8,7 +8,10 @@
  * with -EIO when asked to, and losing a device on request
  * (md5hip_batcher_inject_fault: that submission completes with -EIO and
  * garbage digests, the batcher reports -ENODEV from then on and refuses
- * every submission with it).  Built with ASan+UBSan and with TSan by
+ * every submission with it), or refusing a device's next submission
+ * (g_refuse_next: the device reads healthy until then).  It can log the
+ * device and range of every submission it is handed (g_log_on).  Built with
+ * ASan+UBSan and with TSan by
  * tests/test_pool_host.py.  Exits 0 when every check holds, else prints the
  * failing check.
  */
@@ -65,6 +68,12 @@ int md5hip_batcher_inject_fault(md5hip_batcher *b, uint64_t after)
 static int g_fail_every = 0;       /* every n-th submission (process-wide) fails */
 static uint64_t g_submit_count = 0;
 static pthread_mutex_t g_count_mu = PTHREAD_MUTEX_INITIALIZER;
+/* every md5hip_submit_src call while g_log_on, refused ones too (g_count_mu) */
+static int g_log_on = 0;
+static struct { int dev; uint64_t lo, hi; } g_log[16];
+static int g_nlog = 0;
+/* device g's next submission is refused with -ENODEV and loses the device */
+static int g_refuse_next[4];
 
 int md5hip_batcher_create(int device, uint64_t slice_bytes, uint32_t nslots, md5hip_batcher **out)
 {
@@ -177,6 +186,18 @@ int md5hip_submit_src(md5hip_batcher *b, int kind, uint32_t fastcrc, const struc
     if (ticket) *ticket = 0;
     const uint64_t n = hi - lo;
     if (n == 0) return 0;
+    pthread_mutex_lock(&g_count_mu);
+    if (g_log_on) {
+        if (g_nlog < 16) {
+            g_log[g_nlog].dev = b->device;
+            g_log[g_nlog].lo = lo;
+            g_log[g_nlog].hi = hi;
+        }
+        g_nlog++;
+    }
+    pthread_mutex_unlock(&g_count_mu);
+    if (b->device < 4 && __atomic_exchange_n(&g_refuse_next[b->device], 0, __ATOMIC_ACQ_REL))
+        __atomic_store_n(&b->lost, -ENODEV, __ATOMIC_RELEASE);
     if (md5hip_batcher_health(b)) return -ENODEV;
     const uint32_t dsz = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
     uint64_t weight = 0;
@@ -294,6 +315,130 @@ static void *thread_main(void *arg)
         }
     }
     return NULL;
+}
+
+static void log_start(void)
+{
+    pthread_mutex_lock(&g_count_mu);
+    g_log_on = 1;
+    g_nlog = 0;
+    pthread_mutex_unlock(&g_count_mu);
+}
+
+static int log_stop(void)
+{
+    pthread_mutex_lock(&g_count_mu);
+    g_log_on = 0;
+    const int n = g_nlog;
+    pthread_mutex_unlock(&g_count_mu);
+    return n;
+}
+
+/* the logged calls are exactly the parts [first[g], first[g + 1]) in order,
+ * each on a device of its own */
+static void check_log(int ncalls, const uint64_t *first, const char *what)
+{
+    CHECK(ncalls == 4, "%s: %d submit calls", what, ncalls);
+    unsigned devs = 0;
+    for (int g = 0; g < 4; g++) {
+        CHECK(g_log[g].lo == first[g] && g_log[g].hi == first[g + 1], "%s: part %d is [%llu, %llu), plan [%llu, %llu)",
+              what, g, (unsigned long long)g_log[g].lo, (unsigned long long)g_log[g].hi,
+              (unsigned long long)first[g], (unsigned long long)first[g + 1]);
+        devs |= 1u << g_log[g].dev;
+    }
+    CHECK(devs == 15, "%s: devices %x", what, devs);
+}
+
+/* split submissions are cut where md5hip_pool_plan cuts, for every source kind */
+static void check_parts_follow_plan(md5hip_pool *p, const void *const *ptrs)
+{
+    static unsigned char dig[2000][16];
+    static struct md5hip_iov segs[4000];
+    static uint64_t seg_first[2001];
+    uint64_t first[5], t;
+    CHECK(md5hip_pool_plan(g_lens, 2000, 4, first) == 0, "plan");
+    log_start();
+    CHECK(md5hip_pool_submit_async(p, ptrs, g_lens, 2000, &dig[0][0], &t) == 0, "plan: ptrs");
+    check_log(log_stop(), first, "ptrs");
+    CHECK(md5hip_pool_wait(p, t) == 0, "plan: ptrs wait");
+    for (int i = 0; i < 2000; i++) CHECK(memcmp(dig[i], g_want[i], 16) == 0, "plan: ptrs digest %d", i);
+
+    uint64_t ns = 0;
+    for (int i = 0; i < 2000; i++) {
+        seg_first[i] = ns;
+        const uint32_t h = g_lens[i] / 3;
+        segs[ns++] = (struct md5hip_iov){g_blob + g_offs[i], h};
+        segs[ns++] = (struct md5hip_iov){g_blob + g_offs[i] + h, g_lens[i] - h};
+    }
+    seg_first[2000] = ns;
+    memset(dig, 0, sizeof dig);
+    log_start();
+    CHECK(md5hip_pool_submit_iov_async(p, segs, seg_first, 2000, &dig[0][0], &t) == 0, "plan: iov");
+    check_log(log_stop(), first, "iov");
+    CHECK(md5hip_pool_wait(p, t) == 0, "plan: iov wait");
+    for (int i = 0; i < 2000; i++) CHECK(memcmp(dig[i], g_want[i], 16) == 0, "plan: iov digest %d", i);
+
+    for (uint64_t g = 0; g <= 4; g++) first[g] = 66 * g / 4;
+    log_start();
+    CHECK(md5hip_pool_host_fixed(p, g_blob, 66, 100000, 100000, &dig[0][0]) == 0, "plan: fixed");
+    check_log(log_stop(), first, "fixed");
+    printf("parts follow md5hip_pool_plan\n");
+}
+
+/* 40 synchronous whole submissions from one thread on an idle pool land
+ * evenly on its healthy devices: routing rotates on ties, so a claim left
+ * behind by an earlier submission skews this for good */
+static void check_even_rotation(md5hip_pool *p, const void *const *ptrs)
+{
+    static unsigned char dig[20][16];
+    struct md5hip_batcher_stats a[4], b[4];
+    uint32_t healthy = 0;
+    for (uint32_t g = 0; g < 4; g++) {
+        md5hip_pool_device_stats(p, g, &a[g]);
+        healthy += md5hip_pool_device_health(p, g) == 0;
+    }
+    CHECK(healthy && 40 % healthy == 0, "rotation: %u healthy", healthy);
+    for (int r = 0; r < 40; r++) {
+        CHECK(md5hip_pool_submit(p, ptrs, g_lens, 20, &dig[0][0]) == 0, "rotation submit %d", r);
+        for (int i = 0; i < 20; i++) CHECK(memcmp(dig[i], g_want[i], 16) == 0, "rotation digest %d/%d", r, i);
+    }
+    for (uint32_t g = 0; g < 4; g++) {
+        md5hip_pool_device_stats(p, g, &b[g]);
+        const uint64_t want = md5hip_pool_device_health(p, g) == 0 ? 40 / healthy : 0;
+        CHECK(b[g].submissions - a[g].submissions == want, "rotation: device %u took %llu of 40, not %llu", g,
+              (unsigned long long)(b[g].submissions - a[g].submissions), (unsigned long long)want);
+    }
+}
+
+/* a device that refuses a part or a whole submission (-ENODEV before it took
+ * the chunks) is left for a healthy one, each such move one failover */
+static void check_refused_parts_move(md5hip_pool *p, const void *const *ptrs)
+{
+    static unsigned char dig[2000][16];
+    struct md5hip_pool_health h0, h;
+    uint64_t t;
+    CHECK(md5hip_pool_get_health(p, &h0) == 0 && h0.nfailed == 0, "refuse: healthy at first");
+    __atomic_store_n(&g_refuse_next[2], 1, __ATOMIC_RELEASE);
+    log_start();
+    CHECK(md5hip_pool_submit_async(p, ptrs, g_lens, 2000, &dig[0][0], &t) == 0, "refuse: async split");
+    const int ncalls = log_stop();
+    CHECK(md5hip_pool_wait(p, t) == 0, "refuse: wait");
+    for (int i = 0; i < 2000; i++) CHECK(memcmp(dig[i], g_want[i], 16) == 0, "refuse: digest %d", i);
+    CHECK(ncalls == 5, "refuse: %d submit calls", ncalls);
+    CHECK(md5hip_pool_get_health(p, &h) == 0 && h.failovers == h0.failovers + 1 && h.nfailed == 1 &&
+          h.failed_mask == 4, "refuse: failovers +%llu nfailed %u mask %llx",
+          (unsigned long long)(h.failovers - h0.failovers), h.nfailed, (unsigned long long)h.failed_mask);
+    __atomic_store_n(&g_refuse_next[0], 1, __ATOMIC_RELEASE);
+    __atomic_store_n(&g_refuse_next[1], 1, __ATOMIC_RELEASE);
+    for (int r = 0; r < 6; r++) {
+        memset(dig, 0, 20 * 16);
+        CHECK(md5hip_pool_submit(p, ptrs, g_lens, 20, &dig[0][0]) == 0, "refuse: sync %d", r);
+        for (int i = 0; i < 20; i++) CHECK(memcmp(dig[i], g_want[i], 16) == 0, "refuse: sync digest %d/%d", r, i);
+    }
+    CHECK(md5hip_pool_get_health(p, &h) == 0 && h.failovers == h0.failovers + 3 && h.nfailed == 3 &&
+          h.failed_mask == 7, "refuse: failovers +%llu nfailed %u mask %llx",
+          (unsigned long long)(h.failovers - h0.failovers), h.nfailed, (unsigned long long)h.failed_mask);
+    printf("refused parts move\n");
 }
 
 int main(void)
@@ -433,6 +578,9 @@ int main(void)
     CHECK(md5hip_pool_host_fixed(p, g_blob, 4, 1000, 1000, &fx[0][0]) == -ENODEV, "fixed, all lost");
     md5hip_pool_destroy(p);
     CHECK(md5hip_pool_create(devs, 4, 0, 0, &p) == 0 && p, "create again");
+    check_parts_follow_plan(p, ptrs);
+    check_even_rotation(p, ptrs);
+    printf("idle pool rotates evenly\n");
 
     /* eight threads at once, tickets waited in reverse, half polled first */
     md5hip_pool_set_split(p, 4u << 20);
@@ -446,6 +594,13 @@ int main(void)
         pthread_join(th[k], NULL);
         CHECK(jobs[k].bad == 0 && jobs[k].rc_bad == 0, "thread %d: bad %d rc %d", k, jobs[k].bad, jobs[k].rc_bad);
     }
+
+    /* no claim outlives its submission: not after the threads' whole and
+     * split ones, and not after refused ones on the devices still healthy */
+    md5hip_pool_set_split(p, 0);
+    check_even_rotation(p, ptrs);
+    check_refused_parts_move(p, ptrs);
+    check_even_rotation(p, ptrs);
     md5hip_pool_destroy(p);
     free(g_blob);
     printf("pool ok\n");

@@ -92,7 +92,7 @@ int main(void)
         tk_ring_put(&r, t, -EIO);
         last = t;
     }
-    CHECK(r.nfailed <= TK_FAILED_MAX);
+    CHECK(r.failed.n <= TK_FAILED_MAX);
     CHECK(done(&r, last, &err) == 1 && err == -EIO);
     tk_ring_free(&r);
     printf("tickets ok\n");

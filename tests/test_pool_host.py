@@ -5,8 +5,11 @@ only after a few polls, failing some on purpose.  Routing, whole and split
 submissions, digest placement, split-ticket bookkeeping, per-ticket errors,
 stats, lost devices (a synchronous split part moved off the failed device,
 the device never routed to again, an asynchronous ticket keeping -EIO,
--ENODEV once every device failed) and 8 concurrent submitting threads -- under ASan+UBSan, and under
-ThreadSanitizer for the lock-free routing and the ticket table."""
+-ENODEV once every device failed), split parts cut where md5hip_pool_plan
+cuts for every source kind, claims that end with their submission (an idle
+pool rotates evenly), refused parts moved with one failover each, and 8
+concurrent submitting threads -- under ASan+UBSan, and under ThreadSanitizer
+for the lock-free routing and the ticket table."""
 import os
 import shutil
 import subprocess
@@ -34,6 +37,8 @@ def _build_and_run(name, san, env_extra):
     out = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     assert out.stdout.strip().endswith("pool ok")
+    for phase in ("parts follow md5hip_pool_plan", "idle pool rotates evenly", "refused parts move"):
+        assert phase in out.stdout, phase
 
 
 def test_pool_logic_under_asan():
