@@ -424,8 +424,12 @@ struct md5hip_batcher_stats {
     uint64_t launches;                /* slots launched */
     uint64_t coalesced_launches;      /* launches holding chunks of > 1 ticket */
     uint64_t chunks;                  /* chunks launched */
-    uint64_t bytes_staged;            /* host bytes moved through staging (host_fixed: a pageable
-                                         source's; a wholly pinned one is DMA'd in place, 0) */
+    uint64_t bytes_staged;            /* staging bytes filled per launched slot: each host chunk
+                                         rounded up to its 128-B line (a fastcrc chunk longer than
+                                         2F: 2F), whether memcpy'd into the pinned staging or pulled
+                                         zero-copy from registered pages into the device staging;
+                                         device-resident chunks 0 (host_fixed: a pageable source's
+                                         bytes; a wholly pinned one is DMA'd in place, 0) */
     uint64_t max_chunks_per_launch;
     uint64_t max_tickets_per_launch;
     uint64_t inflight_target, nslots, max_chunks_per_slot;

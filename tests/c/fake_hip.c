@@ -31,12 +31,23 @@
  *     hipErrorLaunchFailure when it completes; once one has, every copy,
  *     kernel and stream wait on the device fails too.  how 1: that kernel's
  *     launch itself fails, and everything after it.  hipStreamQuery reports
- *     the loss either way (what the batcher classifies an enqueue error by).
+ *     the loss either way (what the batcher classifies an enqueue error by);
+ *   - a record log, off until fake_hip_log names a stream (tests/c/slot_check.c):
+ *     every copy, gather table entry, order build, planner choice and hash
+ *     launch is written there with its arguments, each pointer as the
+ *     allocation it lies in -- `dev:SIZE+OFF` (hipMalloc), `mapped:SIZE+OFF`
+ *     (hipHostMalloc, coherent: the arrays a kernel reads in place),
+ *     `pin:SIZE+OFF` (other hipHostMalloc) or `NAME+OFF` for a range the test
+ *     named with fake_hip_name -- so a record says whose memory a call got;
+ *   - fake_hip_sort_refuse_every: every how-manieth stable sort is refused
+ *     (default 3; 0 never, 1 always).
  * Nothing here is part of the product.
  */
 #include <errno.h>
 #include <pthread.h>
+#include <stdarg.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -70,6 +81,101 @@ static void on_stream(hipStream_t stream)
 {
     if (stream && stream->device != t_device)
         __atomic_fetch_add(&fake_hip_wrong_device, 1, __ATOMIC_RELAXED);
+}
+
+/* ------------------------------------------------------------------ record log
+ * Allocations made while the log is on are remembered with their class, so a
+ * pointer is printed as the memory it lies in. */
+FILE *fake_hip_log;
+#define NRANGE 512
+static pthread_mutex_t g_log_mu = PTHREAD_MUTEX_INITIALIZER;
+static struct { uintptr_t lo, hi; char name[24]; int sized; } g_range[NRANGE];
+
+static void range_add(uintptr_t p, size_t len, const char *name, int sized)
+{
+    if (!fake_hip_log || !p) return;
+    pthread_mutex_lock(&g_log_mu);
+    for (int i = 0; i < NRANGE; i++)
+        if (!g_range[i].hi) {
+            g_range[i].lo = p;
+            g_range[i].hi = p + (len ? len : 1);
+            g_range[i].sized = sized;
+            snprintf(g_range[i].name, sizeof g_range[i].name, "%s", name);
+            break;
+        }
+    pthread_mutex_unlock(&g_log_mu);
+}
+
+static void range_del(const void *p)
+{
+    if (!fake_hip_log || !p) return;
+    pthread_mutex_lock(&g_log_mu);
+    for (int i = 0; i < NRANGE; i++)
+        if (g_range[i].hi && g_range[i].lo == (uintptr_t)p) g_range[i].lo = g_range[i].hi = 0;
+    pthread_mutex_unlock(&g_log_mu);
+}
+
+void fake_hip_name(const void *p, size_t len, const char *name) { range_add((uintptr_t)p, len, name, 0); }
+void fake_hip_unname(const void *p) { range_del(p); }
+
+/* `p` as the range it lies in, into buf; "NULL", or "?" for memory nobody named */
+static const char *where(const void *p, char buf[64])
+{
+    if (!p) return "NULL";
+    snprintf(buf, 64, "?");
+    pthread_mutex_lock(&g_log_mu);
+    for (int i = 0; i < NRANGE; i++)
+        if (g_range[i].hi && g_range[i].lo <= (uintptr_t)p && (uintptr_t)p < g_range[i].hi) {
+            if (g_range[i].sized)
+                snprintf(buf, 64, "%s:%zu+%zu", g_range[i].name, (size_t)(g_range[i].hi - g_range[i].lo),
+                         (size_t)((uintptr_t)p - g_range[i].lo));
+            else
+                snprintf(buf, 64, "%s+%zu", g_range[i].name, (size_t)((uintptr_t)p - g_range[i].lo));
+            break;
+        }
+    pthread_mutex_unlock(&g_log_mu);
+    return buf;
+}
+
+void fake_hip_logf(const char *fmt, ...)
+{
+    if (!fake_hip_log) return;
+    va_list ap;
+    va_start(ap, fmt);
+    flockfile(fake_hip_log);
+    vfprintf(fake_hip_log, fmt, ap);
+    fputc('\n', fake_hip_log);
+    funlockfile(fake_hip_log);
+    va_end(ap);
+}
+const char *fake_hip_where(const void *p, char buf[64]) { return where(p, buf); }
+
+/* a descriptor launch: its arrays, and where the first chunks (up to 4) and
+ * the last one lie, with their lengths (also the one-pass stand-ins', slot_check.c) */
+void fake_hip_log_desc(const char *what, int variant, uint64_t n, uint32_t fastcrc, const void *base,
+                       const uint64_t *off, const uint32_t *len, const uint32_t *ord, const void *out)
+{
+    if (!fake_hip_log) return;
+    char b0[64], b1[64], b2[64], b3[64], b4[64], at[400] = "", lens[128] = "";
+    size_t ao = 0, al = 0;
+    for (uint64_t k = 0; k < n; k = k < 3 || k + 1 == n ? k + 1 : n - 1) {
+        ao += (size_t)snprintf(at + ao, sizeof at - ao, "%s%s", k ? "," : "",
+                               where((const void *)((uintptr_t)base + off[k]), b0));
+        al += (size_t)snprintf(lens + al, sizeof lens - al, "%s%u", k ? "," : "", len[k]);
+    }
+    fake_hip_logf("hash|%s|%d|%llu|%u|%s|%s|%s|%s|%s|at=%s|lens=%s", what, variant, (unsigned long long)n,
+                  fastcrc, where(base, b0), where(off, b1), where(len, b2), where(ord, b3), where(out, b4), at,
+                  lens);
+}
+#define log_desc fake_hip_log_desc
+
+static void log_fixed(const char *what, uint64_t n, uint32_t len, uint64_t stride, uint32_t fastcrc,
+                      const void *src, const void *out)
+{
+    if (!fake_hip_log) return;
+    char b0[64], b1[64];
+    fake_hip_logf("hash|%s|%llu|%u|%llu|%u|%s|%s", what, (unsigned long long)n, len, (unsigned long long)stride,
+                  fastcrc, where(src, b0), where(out, b1));
 }
 
 /* device loss (all under g_lose_mu) */
@@ -198,16 +304,22 @@ static void h2d_check(const void *src, size_t len)
     pthread_mutex_unlock(&g_pin_mu);
 }
 
-hipError_t hipMalloc(void **ptr, size_t size) { *ptr = malloc(size ? size : 1); return *ptr ? hipSuccess : hipErrorOutOfMemory; }
+static hipError_t alloc_as(void **ptr, size_t size, const char *cls)
+{
+    *ptr = malloc(size ? size : 1);
+    if (!*ptr) return hipErrorOutOfMemory;
+    range_add((uintptr_t)*ptr, size, cls, 1);
+    return hipSuccess;
+}
+hipError_t hipMalloc(void **ptr, size_t size) { return alloc_as(ptr, size, "dev"); }
 hipError_t hipHostMalloc(void **ptr, size_t size, unsigned int flags)
 {
-    (void)flags;
-    const hipError_t e = hipMalloc(ptr, size);
+    const hipError_t e = alloc_as(ptr, size, (flags & hipHostMallocCoherent) ? "mapped" : "pin");
     if (e == hipSuccess) pin_add(*ptr, size);
     return e;
 }
-hipError_t hipFree(void *ptr) { free(ptr); return hipSuccess; }
-hipError_t hipHostFree(void *ptr) { pin_del(ptr); free(ptr); return hipSuccess; }
+hipError_t hipFree(void *ptr) { range_del(ptr); free(ptr); return hipSuccess; }
+hipError_t hipHostFree(void *ptr) { range_del(ptr); pin_del(ptr); free(ptr); return hipSuccess; }
 hipError_t hipHostRegister(void *hostPtr, size_t sizeBytes, unsigned int flags) { (void)flags; pin_add(hostPtr, sizeBytes); return hipSuccess; }
 hipError_t hipHostUnregister(void *hostPtr) { pin_del(hostPtr); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void **devPtr, void *hstPtr, unsigned int flags) { (void)flags; *devPtr = hstPtr; return hipSuccess; }
@@ -346,6 +458,11 @@ hipError_t hipMemcpyAsync(void *dst, const void *src, size_t sizeBytes, hipMemcp
     const hipError_t e = enqueue_ok(stream);
     if (e != hipSuccess) return e;
     if (kind == hipMemcpyHostToDevice) h2d_check(src, sizeBytes);
+    if (fake_hip_log) {
+        char b0[64], b1[64];
+        fake_hip_logf("copy|%s|%zu|%s|%s", kind == hipMemcpyHostToDevice ? "H2D" : kind == hipMemcpyDeviceToHost ? "D2H" : "other",
+                      sizeBytes, where(dst, b0), where(src, b1));
+    }
     if (sizeBytes) memmove(dst, src, sizeBytes);
     return hipSuccess;
 }
@@ -369,6 +486,7 @@ int md5hip_digest_fixed(const void *d_base, uint64_t n, uint32_t len, uint64_t s
                         unsigned char *d_digests, void *stream)
 {
     if (kernel_begin((hipStream_t)stream)) return -EIO;
+    log_fixed("md5_fixed", n, len, stride, 0, d_base, d_digests);
     for (uint64_t i = 0; i < n; i++) md5_of((const unsigned char *)d_base + i * stride, len, d_digests + 16 * i);
     return 0;
 }
@@ -377,6 +495,7 @@ int crc32hip_fixed(const void *d_base, uint64_t n, uint32_t len, uint64_t stride
                    uint32_t *d_crcs, void *stream)
 {
     if (kernel_begin((hipStream_t)stream)) return -EIO;
+    log_fixed("crc_fixed", n, len, stride, fastcrc, d_base, d_crcs);
     for (uint64_t i = 0; i < n; i++) d_crcs[i] = blk_crc((const unsigned char *)d_base + i * stride, len, fastcrc);
     return 0;
 }
@@ -386,7 +505,7 @@ int md5hip_digest_desc_variant(const void *d_base, const uint64_t *d_offsets, co
                                void *stream, int variant)
 {
     if (kernel_begin((hipStream_t)stream)) return -EIO;
-    (void)variant;
+    log_desc("md5_desc", variant, n, 0, d_base, d_offsets, d_lens, d_order, d_digests);
     if (((uintptr_t)d_digests & 15u) != 0) return -EINVAL;
     for (uint64_t k = 0; k < n; k++)
         if (d_lens[k] == fake_hip_fail_len) return -EIO;
@@ -416,16 +535,19 @@ int crc32hip_desc_variant(const void *d_base, const uint64_t *d_offsets, const u
                           void *stream, int variant)
 {
     if (variant != 0 && variant != 6 && variant != 7) return -EINVAL;
+    log_desc("crc_desc", variant, n, fastcrc, d_base, d_offsets, d_lens, d_order, d_crcs);
     return crc32hip_desc(d_base, d_offsets, d_lens, d_order, n, fastcrc, d_crcs, stream);
 }
 
 int md5hip_lines_choice(int variant, uint64_t unlined_bytes, uint64_t bytes)
 {
+    fake_hip_logf("choice|lines|%d|%llu|%llu", variant, (unsigned long long)unlined_bytes, (unsigned long long)bytes);
     return variant == MD5HIP_DESC_XDMA && 2 * unlined_bytes > bytes ? MD5HIP_DESC_LINES : variant;
 }
 
 int md5hip_crc_desc_choice(uint64_t n, uint64_t mean_len)
 {
+    fake_hip_logf("choice|crc|%llu|%llu", (unsigned long long)n, (unsigned long long)mean_len);
     return (mean_len >= 2048 ? n <= 128 * 256 : n <= 12 * 256) ? 7 : 6;
 }
 
@@ -433,6 +555,13 @@ int md5hip_gather_launch(const struct md5hip_seg *d_segs, uint64_t nseg, unsigne
 {
     on_stream((hipStream_t)stream);
     if (enqueue_ok((hipStream_t)stream) != hipSuccess) return -EIO;
+    if (fake_hip_log) {
+        char b0[64], b1[64];
+        fake_hip_logf("gather|%llu|%s|%s", (unsigned long long)nseg, where(d_segs, b0), where(d_dst, b1));
+        for (uint64_t k = 0; k < nseg; k++)
+            fake_hip_logf("seg|%s|%s|%u", where((const void *)(uintptr_t)d_segs[k].src, b0),
+                          where((const void *)((uintptr_t)d_dst + d_segs[k].dst), b1), d_segs[k].len);
+    }
     for (uint64_t k = 0; k < nseg; k++)
         memmove((void *)((uintptr_t)d_dst + d_segs[k].dst), (const void *)(uintptr_t)d_segs[k].src, d_segs[k].len);
     return 0;
@@ -442,6 +571,10 @@ int md5hip_gather_launch(const struct md5hip_seg *d_segs, uint64_t nseg, unsigne
 int md5hip_plan_desc(const uint32_t *lens, uint64_t n, uint32_t *order)
 {
     if (!lens || !order) return n ? -EINVAL : 0;
+    if (fake_hip_log) {
+        char b0[64], b1[64];
+        fake_hip_logf("plan_desc|%s|%llu|%s", where(lens, b0), (unsigned long long)n, where(order, b1));
+    }
     uint32_t kmax = 0;
     for (uint64_t i = 0; i < n; i++) if ((lens[i] >> 6) + 1 > kmax) kmax = (lens[i] >> 6) + 1;
     uint64_t at = 0;
@@ -473,6 +606,11 @@ int md5hip_order_device(const uint32_t *d_lens, uint64_t n, uint32_t kmax, uint3
 {
     on_stream((hipStream_t)stream);
     if (enqueue_ok((hipStream_t)stream) != hipSuccess) return -EIO;
+    if (fake_hip_log) {
+        char b0[64], b1[64], b2[64];
+        fake_hip_logf("order|device|%s|%llu|%u|%s|%s", where(d_lens, b0), (unsigned long long)n, kmax,
+                      where(d_bucket_next, b1), where(d_order, b2));
+    }
     for (uint64_t i = 0; i < n; i++) {
         const uint32_t k = (d_lens[i] >> 6) + 1;
         if (k > kmax) continue;
@@ -483,11 +621,13 @@ int md5hip_order_device(const uint32_t *d_lens, uint64_t n, uint32_t kmax, uint3
 }
 
 /* the stable longest-first order: a counting sort by key, equal keys in
- * chunk order (md5hip_order_device_stable's contract).  Every third call is
+ * chunk order (md5hip_order_device_stable's contract).  Every third call
+ * (fake_hip_sort_refuse_every: 0 never, 1 every one) is
  * refused with -ENOSPC (scratch too small), so the batcher's fallback to
  * order_scatter runs too. */
 static unsigned long g_sort_calls;
 unsigned long fake_hip_sort_refused;
+unsigned fake_hip_sort_refuse_every = 3;
 uint64_t md5hip_order_stable_scratch(uint64_t n, uint32_t kmax)
 {
     (void)kmax;
@@ -501,7 +641,14 @@ int md5hip_order_device_stable(const uint32_t *d_lens, uint64_t n, uint32_t kmax
     if (enqueue_ok((hipStream_t)stream) != hipSuccess) return -EIO;
     if (n == 0) return 0;
     if (!d_lens || !d_order || !d_scratch || !kmax || scratch_bytes < 4 * n) return -EINVAL;
-    if (__atomic_add_fetch(&g_sort_calls, 1, __ATOMIC_RELAXED) % 3 == 0) {
+    const unsigned every = __atomic_load_n(&fake_hip_sort_refuse_every, __ATOMIC_RELAXED);
+    const int refuse = every && __atomic_add_fetch(&g_sort_calls, 1, __ATOMIC_RELAXED) % every == 0;
+    if (fake_hip_log) {
+        char b0[64], b1[64], b2[64];
+        fake_hip_logf("order|stable|%s|%llu|%u|%s|%s|%s", where(d_lens, b0), (unsigned long long)n, kmax,
+                      where(d_scratch, b1), where(d_order, b2), refuse ? "refused" : "done");
+    }
+    if (refuse) {
         __atomic_fetch_add(&fake_hip_sort_refused, 1, __ATOMIC_RELAXED);
         return -ENOSPC;
     }
