@@ -598,11 +598,14 @@ int md5hip_pool_create(const int *devices, uint32_t ndev, uint64_t slice_bytes, 
 void md5hip_pool_destroy(md5hip_pool *p);
 int md5hip_pool_ndev(const md5hip_pool *p);
 /* The digest kind of later submissions (submissions already made keep
- * theirs); MD5 or CRC32 with a fastcrc window as md5hip_batcher_set_digest. */
+ * theirs); MD5, CRC32 with a fastcrc window, or MD5_CRC32, as
+ * md5hip_batcher_set_digest. */
 int md5hip_pool_set_digest(md5hip_pool *p, int kind, uint32_t fastcrc);
 int md5hip_pool_set_gather(md5hip_pool *p, int mode);
-/* Submissions above `bytes` (sum of chunk lengths) are split over devices;
- * 0 = one batcher slice (the default). */
+/* Submissions whose weight (sum of len + 64 over their chunks, as
+ * md5hip_pool_plan weighs them) is above `bytes` are split over devices, into
+ * min(ceil(weight / bytes), healthy devices, n) parts; a pool with one
+ * healthy device splits nothing.  0 = one batcher slice (the default). */
 int md5hip_pool_set_split(md5hip_pool *p, uint64_t bytes);
 int md5hip_pool_submit(md5hip_pool *p, const void *const *ptrs, const uint32_t *lens, uint64_t n,
                        unsigned char *digests);
@@ -667,7 +670,10 @@ int md5hip_pool_inject_fault(md5hip_pool *p, uint32_t g, uint64_t after);
 /* The pool's split, exposed for callers and tests (host only, synchronous):
  * first[0..nparts] such that part g is chunks [first[g], first[g+1]).
  * lens == NULL: equal counts, first[g] = g*n/nparts.  Otherwise contiguous
- * ranges of near-equal weight, weight(chunk) = len + 64. */
+ * ranges of near-equal weight, weight(chunk) = len + 64: part g starts at
+ * the first chunk whose prefix weight reaches g * total / nparts, and a chunk
+ * that straddles that target goes to the side that holds more of it (so a
+ * part may be empty: the pool submits nothing for it). */
 int md5hip_pool_plan(const uint32_t *lens, uint64_t n, uint32_t nparts, uint64_t *first);
 
 #ifdef __cplusplus
