@@ -676,6 +676,74 @@ int md5hip_pool_inject_fault(md5hip_pool *p, uint32_t g, uint64_t after);
  * part may be empty: the pool submits nothing for it). */
 int md5hip_pool_plan(const uint32_t *lens, uint64_t n, uint32_t nparts, uint64_t *first);
 
+/*
+ * Asynchronous verify and upgrade, compared on the device (ABI version
+ * unchanged: callers find these by symbol).  For the cache-read and
+ * write-verify sites (blk_io.c:665-704, bc_mgr.c:1464-1492), which submit now
+ * and collect later: the digests never cross PCIe, only one `ok` byte per
+ * chunk and a count do.
+ *
+ * md5hip_digest_compare: the kernel alone, on digests already on the device.
+ * ok[i] = (bytes [goff, goff+wsz) of record i of d_got == want i); *d_nbad += mismatches.
+ * d_got: n records of gsz bytes (4, 16 or 32; aligned to min(gsz,16)); d_want: n x wsz
+ * bytes, any alignment; d_ok: n bytes, each written 0 or 1, any alignment; d_nbad: a
+ * device uint64 the kernel ADDS to (may be NULL).  goff, wsz multiples of 4, goff+wsz <= gsz.
+ * Whole-digest verify: goff 0, wsz = gsz.  Upgrade: gsz 32, goff 16, wsz 4.
+ * n == 0: a no-op returning 0; -EINVAL before anything is enqueued.
+ */
+int md5hip_digest_compare(const void *d_got, uint32_t gsz, uint32_t goff, uint32_t wsz,
+                          const void *d_want, uint64_t n, unsigned char *d_ok,
+                          uint64_t *d_nbad, void *stream);
+
+/*
+ * Ticket forms of md5hip_batch_verify_iov / md5hip_batch_upgrade_iov.  The
+ * chunks coalesce into the open slot with everyone else's of the same kind;
+ * the slot's launch is followed by ONE compare launch over its digests, and
+ * `ok` and the counts come back in one copy (a slot whose host submissions
+ * are all whole-digest verifies copies no digests back).  They return 0 or
+ * -errno, not the mismatch count: that is *nbad.
+ *   expected / want_crc   copied by the call: reusable on return
+ *   ok, md5_out, nbad     written when the ticket completes with 0, and must
+ *                         stay valid until then; *nbad (may be NULL) is set to
+ *                         0 by the call and the mismatches are added to it
+ *   *ticket               zeroed first; 0 for an empty submission; served by
+ *                         md5_batch_wait / md5_batch_poll / md5_batch_flush
+ * A launch that fails (-EIO) or never runs (-ENODEV) writes nothing to ok,
+ * md5_out or nbad.  -ENOSYS when the library was built without the compare
+ * kernel, -ENOMEM when the buffers of the feature (allocated by the first
+ * such call, once) cannot be had: nothing is enqueued then.
+ * verify: the batcher's digest kind at the call (MD5_CRC32: whole 32-byte
+ * records); upgrade: MD5_CRC32 for this call, whatever the batcher is set to.
+ */
+int md5hip_batch_verify_iov_async(md5hip_batcher *b, const struct md5hip_iov *segs,
+                                  const uint64_t *seg_first, uint64_t n, const void *expected,
+                                  unsigned char *ok, uint64_t *nbad, uint64_t *ticket);
+int md5hip_batch_upgrade_iov_async(md5hip_batcher *b, const struct md5hip_iov *segs,
+                                   const uint64_t *seg_first, uint64_t n, const uint32_t *want_crc,
+                                   unsigned char *ok, unsigned char *md5_out, uint64_t *nbad,
+                                   uint64_t *ticket);
+/* Verify of device-resident chunks (d_ptrs / lens as md5_batch_submit_device)
+ * under the batcher's digest kind.  expected and ok both on the batcher's
+ * device (on_device != 0: any alignment, expected is read in place and must
+ * stay until completion; ok is undefined after a failed launch) or both on
+ * the host (expected copied by the call).  nbad is host memory either way.
+ * producer_stream / order as md5_batch_submit_device_after; ticket NULL =
+ * synchronous. */
+int md5_batch_verify_device(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens,
+                            uint64_t n, const void *expected, unsigned char *ok, int on_device,
+                            void *producer_stream, int order, uint64_t *nbad, uint64_t *ticket);
+/* On the pool: routed and split like md5hip_pool_submit_iov_async (part
+ * [lo, hi) verifies against expected + wsz lo into ok + lo, md5_out + 16 lo;
+ * every part adds into the one *nbad); md5hip_pool_wait / _poll serve the
+ * tickets.  An asynchronous ticket on a device that fails is not moved. */
+int md5hip_pool_verify_iov_async(md5hip_pool *p, const struct md5hip_iov *segs,
+                                 const uint64_t *seg_first, uint64_t n, const void *expected,
+                                 unsigned char *ok, uint64_t *nbad, uint64_t *ticket);
+int md5hip_pool_upgrade_iov_async(md5hip_pool *p, const struct md5hip_iov *segs,
+                                  const uint64_t *seg_first, uint64_t n, const uint32_t *want_crc,
+                                  unsigned char *ok, unsigned char *md5_out, uint64_t *nbad,
+                                  uint64_t *ticket);
+
 #ifdef __cplusplus
 }
 #endif

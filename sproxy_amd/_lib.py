@@ -166,6 +166,12 @@ def lib():
         "md5crc32hip_plan": (i, [u64, u64]),
         "md5crc32hip_fixed_variant": (i, [vp, u64, u32, u64, vp, vp, i]),
         "md5crc32hip_desc_variant": (i, [vp, vp, vp, vp, u64, vp, vp, i]),
+        "md5hip_digest_compare": (i, [vp, u32, u32, u32, vp, u64, vp, vp, vp]),
+        "md5hip_batch_verify_iov_async": (i, [vp, vp, vp, u64, vp, vp, vp, vp]),
+        "md5hip_batch_upgrade_iov_async": (i, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "md5_batch_verify_device": (i, [vp, vp, vp, u64, vp, vp, i, vp, i, vp, vp]),
+        "md5hip_pool_verify_iov_async": (i, [vp, vp, vp, u64, vp, vp, vp, vp]),
+        "md5hip_pool_upgrade_iov_async": (i, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -205,7 +211,9 @@ EXPORTS = ["MD5Init", "MD5Update", "MD5Final", "nc_MD5Init", "nc_MD5Update", "nc
            "md5hip_batcher_health", "md5hip_batcher_inject_fault", "md5hip_pool_get_health",
            "md5hip_pool_device_health", "md5hip_pool_inject_fault", "md5_batch_submit_device_fixed",
            "md5crc32hip_fixed", "md5crc32hip_desc", "md5hip_batch_upgrade_iov", "md5hip_pool_upgrade_iov",
-           "md5crc32hip_plan", "md5crc32hip_fixed_variant", "md5crc32hip_desc_variant"]
+           "md5crc32hip_plan", "md5crc32hip_fixed_variant", "md5crc32hip_desc_variant",
+           "md5hip_digest_compare", "md5hip_batch_verify_iov_async", "md5hip_batch_upgrade_iov_async",
+           "md5_batch_verify_device", "md5hip_pool_verify_iov_async", "md5hip_pool_upgrade_iov_async"]
 
 
 def check(fn, rc):

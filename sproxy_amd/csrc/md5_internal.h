@@ -165,6 +165,35 @@ static inline int md5hip_digest_usable(int kind, uint32_t fastcrc)
     return 0;
 }
 
+/* One range of the digest-compare kernel's table form (md5_verify.hip): for
+ * i in [0, count), ok[i] = (bytes [goff, goff + wsz) of record first + i of
+ * the launch's digest array == want i), and *cnt = the range's mismatches
+ * (stored, not added: a range is one workgroup's).  want: count x wsz bytes,
+ * ok: count bytes, both device addresses of any alignment; cnt: a device
+ * uint64.  The batcher cuts a long segment into ranges of at most
+ * MD5HIP_CMP_PIECE records; the public entry cuts its n the same way. */
+struct md5hip_cmp {
+    uint64_t first, count;
+    uint64_t want, ok, cnt;
+    uint32_t goff, wsz;
+};
+enum { MD5HIP_CMP_PIECE = 4096 };
+
+/* The table launcher, one workgroup per entry (md5_verify.hip): a weak
+ * reference for the host objects, like the MD5_CRC32 launchers above --
+ * without it the asynchronous verify entries return -ENOSYS before anything
+ * is enqueued.  d_got: records of gsz bytes (4, 16 or 32), aligned to
+ * min(gsz, 16).  0, -EINVAL, -EIO. */
+__attribute__((visibility("hidden")))
+int md5hip_compare_launch(const void *d_got, uint32_t gsz, const struct md5hip_cmp *d_tab, uint64_t nent,
+                          void *stream);
+#ifndef MD5HIP_DEFINES_COMPARE
+extern __typeof__(md5hip_compare_launch) md5hip_compare_launch __attribute__((weak));
+static inline int md5hip_compare_present(void) { return &md5hip_compare_launch != 0; }
+#else
+static inline int md5hip_compare_present(void) { return 1; }
+#endif
+
 /* verify: ok[i] = digest i of `got` equals that of `expected`; the number of
  * mismatches */
 static inline int md5hip_verify_count(const unsigned char *got, const void *expected, uint32_t dsz, uint64_t n,
@@ -224,6 +253,30 @@ int md5hip_submit_src(struct md5hip_batcher *b, int kind, uint32_t fastcrc, cons
                       uint64_t lo, uint64_t hi, unsigned char *digests, uint64_t *ticket, int urgent);
 __attribute__((visibility("hidden")))
 int md5hip_batcher_ticket_state(struct md5hip_batcher *b, uint64_t ticket, int *err);
+
+/* What a verify submission compares and where its results go (all indexed
+ * by the submission's chunk): expected = wsz bytes per chunk, compared with
+ * bytes [goff, goff + wsz) of the chunk's digest; ok = one byte per chunk;
+ * md5_out = 16 bytes per chunk or NULL (upgrade: the records' MD5s, host
+ * only); nbad = a counter the mismatches are ADDED to, atomically, when a
+ * launch retires, or NULL; on_device: expected and ok are device memory.
+ *   md5hip_verify_src   md5hip_submit_src's sibling: chunks [lo, hi) of a
+ *                       source as verify segments, results to ok + lo,
+ *                       md5_out + 16 lo, expected from expected + wsz lo;
+ *                       *nbad is not zeroed (the parts of a pool's
+ *                       submission share it).  -ENOSYS without the compare
+ *                       launcher, -ENOMEM if the batcher's verify buffers
+ *                       cannot be allocated: nothing enqueued either way. */
+struct md5hip_verify_opt {
+    const void *expected;
+    unsigned char *ok, *md5_out;
+    uint64_t *nbad;
+    uint32_t goff, wsz;
+    int on_device;
+};
+__attribute__((visibility("hidden")))
+int md5hip_verify_src(struct md5hip_batcher *b, int kind, uint32_t fastcrc, const struct md5hip_src *src,
+                      uint64_t lo, uint64_t hi, const struct md5hip_verify_opt *v, uint64_t *ticket, int urgent);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,12 @@
 #include "md5_internal.h"
 #include "md5_tickets.h"
 
+/* The batcher's verify submission is a weak reference here, as the compare
+ * launcher is for the batcher (md5_internal.h): a pool linked over stand-in
+ * batchers that have neither refuses the verify tickets with -ENOSYS. */
+extern __typeof__(md5hip_verify_src) md5hip_verify_src __attribute__((weak));
+static inline int verify_present(void) { return md5hip_compare_present() && &md5hip_verify_src; }
+
 #define POOL_MAX_DEV 64
 #define MT_BIT (1ull << 63)
 #define FAILED_MAX (1u << 16)
@@ -457,6 +463,7 @@ struct pool_sub {                      /* what every part of one submission shar
     md5hip_pool *p;
     const struct md5hip_src *s;
     unsigned char *digests;
+    const struct md5hip_verify_opt *v; /* a verify submission (digests NULL): compared on each part's device */
     int kind;
     uint32_t fastcrc;
     int sync;                          /* the caller has no ticket: it waits in the call */
@@ -517,8 +524,11 @@ static int part_place(const struct pool_sub *u, struct pool_part *q, int claimed
     for (;; claimed = 0) {
         if (!claimed && !route(p, 1, q)) return -ENODEV;
         q->t = 0;
-        const int rc = md5hip_submit_src(p->b[q->dev], u->kind, u->fastcrc, u->s, q->lo, q->hi,
-                                         u->digests + (size_t)md5hip_digest_size(u->kind) * q->lo, &q->t, u->sync);
+        const int rc = u->v ? md5hip_verify_src(p->b[q->dev], u->kind, u->fastcrc, u->s, q->lo, q->hi, u->v, &q->t,
+                                                u->sync)
+                            : md5hip_submit_src(p->b[q->dev], u->kind, u->fastcrc, u->s, q->lo, q->hi,
+                                                u->digests + (size_t)md5hip_digest_size(u->kind) * q->lo, &q->t,
+                                                u->sync);
         unclaim(p, q);
         if (rc != -ENODEV || dev_ok(p, q->dev)) return rc;
         count_failover(p);
@@ -623,15 +633,21 @@ static int submit_split(const struct pool_sub *u, uint64_t n, uint64_t total, ui
 
 /* n > 0 valid chunks, *ticket zeroed (pool_enter); ticket NULL =
  * synchronous; kind < 0 = the pool's current digest kind */
-static int pool_submit(md5hip_pool *p, const struct md5hip_src *s, uint64_t n, unsigned char *digests,
-                       uint64_t *ticket, int kind, uint32_t fastcrc)
+static int pool_submit_as(md5hip_pool *p, const struct md5hip_src *s, uint64_t n, unsigned char *digests,
+                          const struct md5hip_verify_opt *v, uint64_t *ticket, int kind, uint32_t fastcrc)
 {
-    struct pool_sub u = {.p = p, .s = s, .digests = digests, .sync = ticket == NULL};
+    struct pool_sub u = {.p = p, .s = s, .digests = digests, .v = v, .sync = ticket == NULL};
     const uint64_t split = sub_open(&u, kind, fastcrc);
     const uint64_t total = src_total(s, n);
     const uint32_t k = part_count(p, n, total, split);
     if (k == 0) return -ENODEV;
     return k == 1 ? submit_whole(&u, n, total, ticket) : submit_split(&u, n, total, k, ticket);
+}
+
+static int pool_submit(md5hip_pool *p, const struct md5hip_src *s, uint64_t n, unsigned char *digests,
+                       uint64_t *ticket, int kind, uint32_t fastcrc)
+{
+    return pool_submit_as(p, s, n, digests, NULL, ticket, kind, fastcrc);
 }
 
 /* ------------------------------------------------------------------------
@@ -728,4 +744,52 @@ int md5hip_pool_upgrade_iov(md5hip_pool *p, const struct md5hip_iov *segs, const
     if (rc == 0) rc = md5hip_upgrade_count(rec, want_crc, n, ok, md5_out);
     free(rec);
     return rc;
+}
+
+/* The ticket forms of verify and upgrade: the submission routed and split as
+ * any other, each part compared on its own device (md5hip_verify_src) and
+ * adding its mismatches into the one *nbad, zeroed here.  kind < 0: the
+ * pool's digest kind, whole digests (v->wsz is set from it). */
+static int pool_enter_verify(md5hip_pool *p, const struct md5hip_iov *segs, const uint64_t *seg_first, uint64_t n,
+                             int kind, struct md5hip_verify_opt *v, uint64_t *ticket)
+{
+    if (ticket) *ticket = 0;
+    if (!p || !ticket) return -EINVAL;
+    if (v->nbad) *v->nbad = 0;
+    if (!verify_present()) return -ENOSYS;
+    if (n == 0) return 0;
+    if (!v->expected || !v->ok) return -EINVAL;
+    uint32_t fastcrc = 0;
+    if (kind < 0) {                               /* one snapshot for the digest size and the submission */
+        pthread_mutex_lock(&p->mu);
+        kind = p->kind;
+        fastcrc = p->fastcrc;
+        pthread_mutex_unlock(&p->mu);
+        v->wsz = md5hip_digest_size(kind);
+    }
+    int rc = md5hip_digest_usable(kind, fastcrc);
+    if (rc) return rc;
+    const struct md5hip_src s = {.kind = MD5HIP_SRC_IOV, .segs = segs, .seg_first = seg_first};
+    if ((rc = md5hip_src_check(&s, n))) return rc;
+    return pool_submit_as(p, &s, n, NULL, v, ticket, kind, fastcrc);
+}
+
+int md5hip_pool_verify_iov_async(md5hip_pool *p, const struct md5hip_iov *segs, const uint64_t *seg_first,
+                                 uint64_t n, const void *expected, unsigned char *ok, uint64_t *nbad,
+                                 uint64_t *ticket)
+{
+    struct md5hip_verify_opt v = {.expected = expected, .ok = ok, .nbad = nbad};
+    return pool_enter_verify(p, segs, seg_first, n, -1, &v, ticket);
+}
+
+int md5hip_pool_upgrade_iov_async(md5hip_pool *p, const struct md5hip_iov *segs, const uint64_t *seg_first,
+                                  uint64_t n, const uint32_t *want_crc, unsigned char *ok, unsigned char *md5_out,
+                                  uint64_t *nbad, uint64_t *ticket)
+{
+    struct md5hip_verify_opt v = {.expected = want_crc, .ok = ok, .md5_out = md5_out, .nbad = nbad, .goff = 16, .wsz = 4};
+    if (p && ticket && n && !md5_out) {
+        *ticket = 0;
+        return -EINVAL;
+    }
+    return pool_enter_verify(p, segs, seg_first, n, MD5HIP_DIGEST_MD5_CRC32, &v, ticket);
 }

@@ -62,6 +62,8 @@
  *                            tables), the engines submit and fixed_submit,
  *                            wait / poll / flush
  *   entries                  the C ABI's submit calls; the pool's; verify
+ *   asynchronous verify      the ticket forms: verify segments compared on
+ *                            the device (enqueue_verify), their buffers
  * The ticket table is md5_tickets.h, the host chunk sources (segments,
  * copies, the threaded gather) md5_source.h: both included here alone.
  */
@@ -205,6 +207,17 @@ struct seg {
     uint64_t ticket, first, count;
     unsigned char *user;
     int on_device;
+    /* a verify segment (ok != NULL, user == NULL): its chunks' digests are
+     * compared on the device (enqueue_verify) instead of delivered.  ok / the
+     * expected values at `want` are host memory, or (on_device) the caller's
+     * device memory; a host caller's expected values were copied into the
+     * slot's table buffer at submit time (want = their offset there).
+     * md5_out: upgrade, the records' MD5s (host).  The range's compare
+     * entries are [ent, ent + nent) of the slot's table. */
+    unsigned char *ok, *md5_out;
+    uint64_t *nbad;
+    uint64_t want;
+    uint32_t goff, wsz, ent, nent;
 };
 
 struct slot {
@@ -283,6 +296,15 @@ struct slot {
     int urgent;
     /* md5hip_batcher_inject_fault: this launch completes as a device fault */
     int inject;
+    /* verify segments (struct seg): how many the slot holds, the bytes of host
+     * callers' expected values copied into h_vin so far, and the compare
+     * entries of its launch.  h_vin / d_vin (expected values, then the table)
+     * and h_vout / d_vout (one count per entry, then an ok byte per chunk) are
+     * the slot's share of the batcher's verify buffers: NULL until the first
+     * verify submission (verify_buffers) */
+    uint32_t nverify, nvent;
+    uint64_t vwant;
+    unsigned char *h_vin, *d_vin, *h_vout, *d_vout;
 };
 enum { WATCH_NONE = 0, WATCH_ACTIVE, WATCH_GAVE_UP };
 
@@ -316,6 +338,11 @@ struct md5hip_batcher {
     hipEvent_t after_ev;     /* recorded on a producer's stream (md5_batch_submit_device_on) */
     int failed;               /* 0, or -ENODEV once the device failed (sticky; read lock-free by the pool) */
     uint64_t inject_at;       /* md5hip_batcher_inject_fault: launch number that faults, 0 = none */
+    /* verify buffers of all slots, allocated by the first verify submission
+     * (verify_buffers): pinned host and device, `vin_sz` / `vout_sz` per slot */
+    unsigned char *vb_hin, *vb_din, *vb_hout, *vb_dout;
+    uint64_t vin_sz, vout_sz;
+    int vready;
 };
 
 #define CK(x) do { if ((x) != hipSuccess) { rc = -ENODEV; goto fail; } } while (0)
@@ -557,6 +584,51 @@ static int enqueue_kernel(struct slot *sl, unsigned char *dst)
     return hipEventRecord(sl->kdone, sl->stream) ? -EIO : 0;
 }
 
+/* The slot's verify segments, compared where the digests are (behind kdone,
+ * like the scatter: a chained launch does not wait on it): the table of
+ * compare entries -- a segment cut into ranges of MD5HIP_CMP_PIECE chunks,
+ * one workgroup each -- goes up behind the host callers' expected values in
+ * ONE copy, ONE launch compares over d_dig, and the entries' counts and the
+ * host callers' ok bytes come back in ONE copy.  Device callers' expected
+ * values are read and their ok bytes written in place.  The table has room:
+ * verify_buffers sized it for maxn chunks in segcap segments. */
+static int enqueue_verify(struct slot *sl)
+{
+    uint32_t nent = 0;
+    int host_ok = 0;
+    for (uint32_t k = 0; k < sl->nsegs; k++)
+        if (sl->segs[k].ok) nent += (uint32_t)((sl->segs[k].count + MD5HIP_CMP_PIECE - 1) / MD5HIP_CMP_PIECE);
+    const uint64_t tab_at = (sl->vwant + 15) & ~15ull;
+    struct md5hip_cmp *tab = (struct md5hip_cmp *)(sl->h_vin + tab_at);
+    unsigned char *d_ok = sl->d_vout + 8 * (size_t)nent;      /* ok byte of slot chunk c: d_ok + c */
+    uint32_t e = 0;
+    for (uint32_t k = 0; k < sl->nsegs; k++) {
+        struct seg *g = &sl->segs[k];
+        if (!g->ok) continue;
+        const uint64_t want = g->on_device ? g->want : (uint64_t)(uintptr_t)sl->d_vin + g->want;
+        const uint64_t ok = (uint64_t)(uintptr_t)(g->on_device ? g->ok : d_ok + g->first);
+        host_ok |= !g->on_device;
+        g->ent = e;
+        for (uint64_t at = 0; at < g->count; at += MD5HIP_CMP_PIECE, e++) {
+            const uint64_t c = g->count - at < MD5HIP_CMP_PIECE ? g->count - at : MD5HIP_CMP_PIECE;
+            tab[e] = (struct md5hip_cmp){g->first + at, c, want + (uint64_t)g->wsz * at, ok + at,
+                                         (uint64_t)(uintptr_t)(sl->d_vout + 8 * (size_t)e), g->goff, g->wsz};
+        }
+        g->nent = e - g->ent;
+    }
+    sl->nvent = nent;
+    if (hipMemcpyAsync(sl->d_vin, sl->h_vin, tab_at + sizeof(struct md5hip_cmp) * nent, hipMemcpyHostToDevice,
+                       sl->stream))
+        return -EIO;
+    const int rc = md5hip_compare_launch(sl->d_dig, sl->dsz, (const struct md5hip_cmp *)(sl->d_vin + tab_at), nent,
+                                         sl->stream);
+    if (rc) return rc;
+    return hipMemcpyAsync(sl->h_vout, sl->d_vout, 8 * (size_t)nent + (host_ok ? sl->n : 0), hipMemcpyDeviceToHost,
+                          sl->stream)
+               ? -EIO
+               : 0;
+}
+
 /* Digests out: one D2H for the host segments, one scatter for the device
  * ones, then `done`.  The scatter kernel runs one workgroup per entry, so a
  * long segment is cut into pieces of DSC_PIECE bytes as the table has room
@@ -569,10 +641,12 @@ static int enqueue_digests(md5hip_batcher *b, struct slot *sl)
     int any_host = 0;
     sl->ndsc = 0;
     uint64_t ndev = 0;
-    for (uint32_t k = 0; k < sl->nsegs && !sl->direct; k++) ndev += sl->segs[k].on_device;
+    for (uint32_t k = 0; k < sl->nsegs && !sl->direct; k++) ndev += sl->segs[k].on_device && !sl->segs[k].ok;
     uint64_t spare = b->segcap - ndev;                   /* nsegs < segcap (slot_open) */
     for (uint32_t k = 0; k < sl->nsegs && !sl->direct; k++) {
         const struct seg *g = &sl->segs[k];
+        /* a verify segment takes no digests, but an upgrade's MD5s (host) */
+        if (g->ok) { any_host |= g->md5_out != NULL; continue; }
         if (!g->on_device) { any_host = 1; continue; }
         const uint64_t len = (uint64_t)sl->dsz * g->count;
         if (len == 0) continue;
@@ -594,6 +668,7 @@ static int enqueue_digests(md5hip_batcher *b, struct slot *sl)
             return -EIO;
         if ((rc = md5hip_gather_launch(sl->d_dsc, sl->ndsc, sl->d_dig, sl->stream))) return rc;
     }
+    if (sl->nverify && (rc = enqueue_verify(sl))) return rc;
     if (any_host &&
         hipMemcpyAsync(sl->h_dig, sl->d_dig, (size_t)sl->dsz * n, hipMemcpyDeviceToHost, sl->stream))
         return -EIO;
@@ -608,7 +683,7 @@ static int slot_enqueue(md5hip_batcher *b, struct slot *sl)
      * order: the kernel writes them in place (no scatter launch) */
     const struct seg *g0 = sl->nsegs == 1 ? &sl->segs[0] : NULL;
     unsigned char *dst = sl->d_dig;
-    if (g0 && g0->on_device && g0->first == 0 && g0->count == sl->n && ((uintptr_t)g0->user & 15u) == 0) {
+    if (g0 && g0->on_device && !g0->ok && g0->first == 0 && g0->count == sl->n && ((uintptr_t)g0->user & 15u) == 0) {
         dst = g0->user;
         sl->direct = 1;
     }
@@ -632,6 +707,8 @@ static void slot_reset(struct slot *sl)
     sl->writers = sl->full = sl->flush = sl->err = sl->direct = 0;
     sl->n = sl->used = sl->nseg = sl->ndma = sl->ndsc = 0;
     sl->nsegs = 0;
+    sl->nverify = sl->nvent = 0;
+    sl->vwant = 0;
     sl->tickets_in = 0;
     sl->copied_n = sl->planned_n = sl->seen_n = 0;
     sl->load = 0;
@@ -643,12 +720,32 @@ static void slot_reset(struct slot *sl)
     sl->hovf = 0;
 }
 
+/* A finished launch's verify segment to its caller: ok (host callers), the
+ * upgrade's MD5s from the records, then its entries' mismatches added into
+ * *nbad -- atomically: the parts of a pool's submission share the counter,
+ * and retire on several batchers. */
+static void verify_deliver(const struct slot *sl, const struct seg *g)
+{
+    if (!g->on_device) memcpy(g->ok, sl->h_vout + 8 * (size_t)sl->nvent + g->first, g->count);
+    for (uint64_t i = 0; g->md5_out && i < g->count; i++)
+        memcpy(g->md5_out + 16 * i, sl->h_dig + 32 * (size_t)(g->first + i), 16);
+    if (!g->nbad) return;
+    uint64_t bad = 0, c;
+    for (uint32_t e = g->ent; e < g->ent + g->nent; e++) {
+        memcpy(&c, sl->h_vout + 8 * (size_t)e, 8);
+        bad += c;
+    }
+    __atomic_fetch_add(g->nbad, bad, __ATOMIC_RELAXED);
+}
+
 /* Deliver a finished (or failed) slot to its tickets and free it (mu held). */
 static void slot_retire(md5hip_batcher *b, struct slot *sl, int err)
 {
     for (uint32_t k = 0; k < sl->nsegs; k++) {
         const struct seg *g = &sl->segs[k];
-        if (!err && !g->on_device)
+        if (g->ok) {
+            if (!err) verify_deliver(sl, g);
+        } else if (!err && !g->on_device)
             memcpy(g->user, sl->h_dig + (size_t)sl->dsz * g->first, (size_t)sl->dsz * g->count);
         tk_ring_put(&b->tk, g->ticket, err);
     }
@@ -1150,6 +1247,10 @@ static void batcher_free(md5hip_batcher *b)
         pthread_cond_destroy(&sl->cv);
     }
     free(b->s);
+    if (b->vb_hin) hipHostFree(b->vb_hin);
+    if (b->vb_hout) hipHostFree(b->vb_hout);
+    if (b->vb_din) hipFree(b->vb_din);
+    if (b->vb_dout) hipFree(b->vb_dout);
     if (b->after_ev) hipEventDestroy(b->after_ev);
     tk_ring_free(&b->tk);
     pthread_mutex_destroy(&b->mu);
@@ -1608,6 +1709,7 @@ struct sub_opt {
     int kind;
     uint32_t fastcrc;
     const hipStream_t *after;
+    const struct md5hip_verify_opt *verify;   /* verify segments (digests NULL): enter_verify */
 };
 
 /* One submission between sub_begin and sub_end: the caller's device (entered
@@ -1683,6 +1785,31 @@ static void slot_after(md5hip_batcher *b, struct slot *sl, const hipStream_t *af
         sl->err = -EIO;
 }
 
+/* Makes `sg` -- chunks [i, i + sg->count) of a verify submission, going into
+ * slot `sl` -- a verify segment (mu held).  A host caller's expected values
+ * are copied into the slot's table buffer here, so the caller may reuse its
+ * array on return (16 to 32 bytes a chunk: beside the chunk's own bytes,
+ * nothing); they fit: verify_buffers sized it for maxn chunks in segcap
+ * segments. */
+static void seg_verify(struct slot *sl, struct seg *sg, const struct md5hip_verify_opt *v, uint64_t i)
+{
+    const unsigned char *want = (const unsigned char *)v->expected + (size_t)v->wsz * i;
+    sg->ok = v->ok + i;
+    sg->md5_out = v->md5_out ? v->md5_out + 16 * (size_t)i : NULL;
+    sg->nbad = v->nbad;
+    sg->goff = v->goff;
+    sg->wsz = v->wsz;
+    if (v->on_device) {
+        sg->want = (uint64_t)(uintptr_t)want;
+    } else {
+        const uint64_t bytes = (uint64_t)v->wsz * sg->count;
+        sg->want = sl->vwant;
+        memcpy(sl->h_vin + sl->vwant, want, bytes);
+        sl->vwant += (bytes + 15) & ~15ull;
+    }
+    sl->nverify++;
+}
+
 /* The submission engine: chunks [0, n) of a PTRS, IOV or DEVICE source into
  * the open slot, as many slots as they take. */
 static int submit(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, const struct sub_opt *o)
@@ -1731,7 +1858,9 @@ static int submit(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, c
             desc_copy(sl) && !sl->err)
             sl->err = -EIO;
         slot_after(b, sl, o->after);
-        if ((rc = seg_push(b, sl, (struct seg){s.t, at, m, o->digests + (size_t)s.dsz * i, o->on_device}))) {
+        struct seg sg = {s.t, at, m, o->verify ? NULL : o->digests + (size_t)s.dsz * i, o->on_device};
+        if (o->verify) seg_verify(sl, &sg, o->verify, i);
+        if ((rc = seg_push(b, sl, sg))) {
             sl->err = rc;                    /* its reserved chunks have no segment */
             break;
         }
@@ -2129,4 +2258,139 @@ int md5hip_batch_upgrade_iov(md5hip_batcher *b, const struct md5hip_iov *segs,
     rc = md5hip_upgrade_count(rec, want_crc, n, ok, md5_out);
     free(rec);
     return rc;
+}
+
+/* ------------------------------------------------------------------------
+ * Asynchronous verify and upgrade: the digests compared on the device
+ * ------------------------------------------------------------------------ */
+/* The verify buffers of every slot, allocated once by the first verify
+ * submission (a batcher that never verifies allocates nothing for it):
+ *   in    host callers' expected values (at most 32 B a chunk, each segment's
+ *         on a 16-B boundary), then the table: a segment of c chunks is
+ *         ceil(c / MD5HIP_CMP_PIECE) entries, so a slot's maxn chunks in
+ *         fewer than segcap segments are fewer than `ents`;
+ *   out   a count per entry, then an ok byte per chunk.
+ * 0, -ENODEV, or -ENOMEM with nothing allocated. */
+static int verify_buffers(md5hip_batcher *b)
+{
+    if (__atomic_load_n(&b->vready, __ATOMIC_ACQUIRE)) return 0;
+    struct dev_guard g;
+    if (batcher_enter(b, &g)) return -ENODEV;
+    int rc = 0;
+    if (!b->vready) {
+        const uint64_t ents = b->segcap + b->maxn / MD5HIP_CMP_PIECE + 1;
+        const uint64_t vin = 32 * b->maxn + 16 * b->segcap + 16 + sizeof(struct md5hip_cmp) * ents;
+        const uint64_t vout = (8 * ents + b->maxn + 15) & ~15ull;
+        void *hin = NULL, *din = NULL, *hout = NULL, *dout = NULL;
+        if (hipHostMalloc(&hin, vin * b->nslots, hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc(&hout, vout * b->nslots, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(&din, vin * b->nslots) != hipSuccess || hipMalloc(&dout, vout * b->nslots) != hipSuccess) {
+            (void)hipGetLastError();
+            if (hin) hipHostFree(hin);
+            if (hout) hipHostFree(hout);
+            if (din) hipFree(din);
+            if (dout) hipFree(dout);
+            rc = -ENOMEM;
+        } else {
+            b->vb_hin = hin; b->vb_din = din; b->vb_hout = hout; b->vb_dout = dout;
+            b->vin_sz = vin;
+            b->vout_sz = vout;
+            for (uint32_t k = 0; k < b->nslots; k++) {
+                b->s[k].h_vin = b->vb_hin + vin * k;
+                b->s[k].d_vin = b->vb_din + vin * k;
+                b->s[k].h_vout = b->vb_hout + vout * k;
+                b->s[k].d_vout = b->vb_dout + vout * k;
+            }
+            __atomic_store_n(&b->vready, 1, __ATOMIC_RELEASE);
+        }
+    }
+    batcher_leave(b, &g);
+    return rc;
+}
+
+/* What every verify entry does once it has named its source, its digest
+ * kind and what is compared: the checks (in the order in which the errors
+ * win: arguments, the launcher, the buffers), then the engine.  Verify
+ * segments never go the FIXED way. */
+static int enter_verify(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, int kind, uint32_t fastcrc,
+                        const struct md5hip_verify_opt *v, int async, uint64_t *ticket, const hipStream_t *after)
+{
+    if (ticket) *ticket = 0;
+    if (!b || (async && !ticket)) return -EINVAL;
+    int rc = md5hip_digest_usable(kind, fastcrc);
+    if (rc) return rc;
+    if (!md5hip_compare_present()) return -ENOSYS;
+    if (n == 0) return 0;
+    if (!v->expected || !v->ok || v->wsz == 0 || ((v->goff | v->wsz) & 3u) ||
+        (uint64_t)v->goff + v->wsz > md5hip_digest_size(kind) || (v->md5_out && v->on_device))
+        return -EINVAL;
+    if ((rc = md5hip_src_check(src, n)) || (rc = verify_buffers(b))) return rc;
+    return submit(b, src, n, &(struct sub_opt){.on_device = v->on_device, .async = async, .ticket = ticket,
+                                               .kind = kind, .fastcrc = fastcrc, .after = after, .verify = v});
+}
+
+int md5hip_verify_src(md5hip_batcher *b, int kind, uint32_t fastcrc, const struct md5hip_src *src, uint64_t lo,
+                      uint64_t hi, const struct md5hip_verify_opt *v, uint64_t *ticket, int urgent)
+{
+    struct md5hip_src part = *src;
+    part.first += lo;
+    struct md5hip_verify_opt pv = *v;
+    if (pv.expected) pv.expected = (const unsigned char *)v->expected + (size_t)v->wsz * lo;
+    if (pv.ok) pv.ok = v->ok + lo;
+    if (pv.md5_out) pv.md5_out = v->md5_out + 16 * (size_t)lo;
+    return enter_verify(b, &part, hi - lo, kind, fastcrc, &pv, ticket ? (urgent ? 2 : 1) : 0, ticket, NULL);
+}
+
+/* The ticket forms: *nbad is zeroed by the call, the mismatches added as
+ * each launch holding the submission's chunks retires. */
+int md5hip_batch_verify_iov_async(md5hip_batcher *b, const struct md5hip_iov *segs, const uint64_t *seg_first,
+                                  uint64_t n, const void *expected, unsigned char *ok, uint64_t *nbad,
+                                  uint64_t *ticket)
+{
+    if (ticket) *ticket = 0;
+    if (!b || !ticket) return -EINVAL;
+    if (nbad) *nbad = 0;
+    if (n && (!expected || !ok)) return -EINVAL;
+    int kind = MD5HIP_DIGEST_MD5;
+    uint32_t fastcrc = 0;
+    if (n) md5hip_batcher_get_digest(b, &kind, &fastcrc);
+    const struct md5hip_src src = src_iov(segs, seg_first);
+    return enter_verify(b, &src, n, kind, fastcrc,
+                        &(struct md5hip_verify_opt){.expected = expected, .ok = ok, .nbad = nbad,
+                                                    .wsz = md5hip_digest_size(kind)},
+                        1, ticket, NULL);
+}
+
+int md5hip_batch_upgrade_iov_async(md5hip_batcher *b, const struct md5hip_iov *segs, const uint64_t *seg_first,
+                                   uint64_t n, const uint32_t *want_crc, unsigned char *ok, unsigned char *md5_out,
+                                   uint64_t *nbad, uint64_t *ticket)
+{
+    if (ticket) *ticket = 0;
+    if (!b || !ticket) return -EINVAL;
+    if (nbad) *nbad = 0;
+    if (n && (!want_crc || !ok || !md5_out)) return -EINVAL;
+    const struct md5hip_src src = src_iov(segs, seg_first);
+    return enter_verify(b, &src, n, MD5HIP_DIGEST_MD5_CRC32, 0,
+                        &(struct md5hip_verify_opt){.expected = want_crc, .ok = ok, .md5_out = md5_out, .nbad = nbad,
+                                                    .goff = 16, .wsz = 4},
+                        1, ticket, NULL);
+}
+
+int md5_batch_verify_device(md5hip_batcher *b, const uint64_t *d_ptrs, const uint32_t *lens, uint64_t n,
+                            const void *expected, unsigned char *ok, int on_device, void *producer_stream,
+                            int order, uint64_t *nbad, uint64_t *ticket)
+{
+    if (ticket) *ticket = 0;
+    if (!b) return -EINVAL;
+    if (nbad) *nbad = 0;
+    if (n && (!expected || !ok)) return -EINVAL;
+    int kind = MD5HIP_DIGEST_MD5;
+    uint32_t fastcrc = 0;
+    if (n) md5hip_batcher_get_digest(b, &kind, &fastcrc);
+    const struct md5hip_src src = src_device(d_ptrs, lens);
+    const hipStream_t after = (hipStream_t)producer_stream;
+    return enter_verify(b, &src, n, kind, fastcrc,
+                        &(struct md5hip_verify_opt){.expected = expected, .ok = ok, .nbad = nbad,
+                                                    .wsz = md5hip_digest_size(kind), .on_device = on_device != 0},
+                        ticket != NULL, ticket, order ? &after : NULL);
 }

@@ -237,6 +237,36 @@ def crc32_desc(base, offsets, lens, order=None, fastcrc: int = 0, out=None, stre
     return out
 
 
+def digest_compare(got, want, gsz: int, goff: int = 0, wsz: int = None, n: int = None, ok=None,
+                   nbad=None, stream=None):
+    """md5hip_digest_compare: ok[i] = (bytes [goff, goff + wsz) of record i of
+    `got` == want i) for n records of gsz bytes (4, 16 or 32), all device
+    tensors; `want` (n x wsz bytes) and `ok` (n bytes, new when None) of any
+    alignment.  `nbad`: a one-element int64 device tensor the mismatches are
+    ADDED to (None: not counted).  Whole-digest compare by default (wsz =
+    gsz); the upgrade shape is gsz 32, goff 16, wsz 4.  Returns ok."""
+    _need_cuda(got, "got")
+    _need_cuda(want, "want")
+    wsz = gsz if wsz is None else wsz
+    if n is None:
+        n = got.numel() * got.element_size() // gsz if gsz else 0
+    if got.numel() * got.element_size() < n * gsz or want.numel() * want.element_size() < n * wsz:
+        raise ValueError("got / want hold fewer than n records")
+    if ok is None:
+        ok = torch.empty(n, dtype=torch.uint8, device=got.device)
+    _need_cuda(ok, "ok")
+    if ok.numel() * ok.element_size() < n:
+        raise ValueError("ok holds fewer than n bytes")
+    if nbad is not None:
+        _need_cuda(nbad, "nbad")
+        if nbad.dtype != torch.int64 or nbad.numel() < 1:
+            raise TypeError("nbad must be an int64 device tensor")
+    check("md5hip_digest_compare",
+          lib().md5hip_digest_compare(got.data_ptr(), gsz, goff, wsz, want.data_ptr(), n, ok.data_ptr(),
+                                      nbad.data_ptr() if nbad is not None else None, _stream(stream)))
+    return ok
+
+
 MD5CRC32_VARIANTS = {"auto": 0, "xdma16": 1, "fedsplit": 2}   # enum md5crc32hip_variant
 MD5CRC32_FEDSPLIT_MIN_LEN = 1024                             # MD5CRC32HIP_FEDSPLIT_MIN_LEN
 
@@ -442,7 +472,9 @@ class Batcher:
                submit_device_fixed="md5_batch_submit_device_fixed",
                set_inflight="md5hip_batcher_set_inflight",
                set_linger="md5hip_batcher_set_linger", set_chain="md5hip_batcher_set_chain",
-               stats="md5hip_batcher_get_stats", inject_fault="md5hip_batcher_inject_fault")
+               stats="md5hip_batcher_get_stats", inject_fault="md5hip_batcher_inject_fault",
+               verify_iov_async="md5hip_batch_verify_iov_async",
+               upgrade_iov_async="md5hip_batch_upgrade_iov_async", verify_device="md5_batch_verify_device")
 
     def __init__(self, device: int = 0, slice_bytes: int = 0, nslots: int = 0,
                  kind: int = 0, fastcrc: int = 0):
@@ -737,6 +769,106 @@ class Batcher:
         del keep
         return ok[:n].astype(bool), md5s[:n]
 
+    class PendingVerify(Pending):
+        """An asynchronous verify or upgrade: keeps the page list, the `ok`
+        array, the mismatch counter, the upgrade's MD5 array and (device
+        form) the expected values alive until the ticket completes.  .wait()
+        returns (ok, nbad), or (ok, md5, nbad) for an upgrade; ok is a bool
+        array, or the caller's device tensor in the on-device form."""
+
+        def __init__(self, batcher, ticket, n, ok, nbad, md5, keep, on_device=False):
+            super().__init__(batcher, ticket, ok, n, keep, on_device)
+            self._nbad, self._md5 = nbad, md5
+
+        def wait(self):
+            check(*self.batcher._call("wait", ctypes.c_uint64(self.ticket)))
+            self._keep = None
+            ok = self._out if self.on_device else self._out[:self.n].astype(bool)
+            nbad = int(self._nbad[0])
+            return (ok, nbad) if self._md5 is None else (ok, self._md5[:self.n], nbad)
+
+    def verify_iov_async(self, chunks, expected) -> "Batcher.PendingVerify":
+        """md5hip_batch_verify_iov_async: submit now, collect later.  The
+        digests are compared on the device; .wait() returns (ok, nbad).
+        `expected` is copied by the call."""
+        arr, fa, keep = self._iov(chunks)
+        n = len(chunks)
+        exp = np.ascontiguousarray(expected)
+        if exp.nbytes != n * self.dsz:
+            raise ValueError("expected must hold one digest per chunk")
+        ok = np.empty(max(n, 1), dtype=np.uint8)
+        nbad = np.zeros(1, dtype=np.uint64)
+        t = ctypes.c_uint64()
+        check(*self._call("verify_iov_async", arr, fa.ctypes.data, n, exp.ctypes.data, ok.ctypes.data,
+                          nbad.ctypes.data, ctypes.byref(t)))
+        return Batcher.PendingVerify(self, t.value, n, ok, nbad, None, (keep, arr, fa))
+
+    def upgrade_iov_async(self, chunks, want_crc) -> "Batcher.PendingVerify":
+        """md5hip_batch_upgrade_iov_async: .wait() returns (ok, md5, nbad) --
+        ok[i] = crc32(chunks[i]) == want_crc[i] compared on the device, and
+        the MD5 of every chunk."""
+        arr, fa, keep = self._iov(chunks)
+        n = len(chunks)
+        want = np.ascontiguousarray(want_crc, dtype=np.uint32)
+        if want.size != n:
+            raise ValueError("want_crc must hold one CRC-32 per chunk")
+        ok = np.empty(max(n, 1), dtype=np.uint8)
+        md5s = np.empty((max(n, 1), 16), dtype=np.uint8)
+        nbad = np.zeros(1, dtype=np.uint64)
+        t = ctypes.c_uint64()
+        check(*self._call("upgrade_iov_async", arr, fa.ctypes.data, n, want.ctypes.data, ok.ctypes.data,
+                          md5s.ctypes.data, nbad.ctypes.data, ctypes.byref(t)))
+        return Batcher.PendingVerify(self, t.value, n, ok, nbad, md5s, (keep, arr, fa))
+
+    def _verify_device(self, ptrs, lens, expected, ok, after, ticket):
+        P = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        L = np.ascontiguousarray(lens, dtype=np.uint32)
+        if P.size != L.size:
+            raise ValueError("ptrs and lens differ in length")
+        n = P.size
+        on_dev = torch is not None and isinstance(expected, torch.Tensor)
+        if on_dev:
+            for t_, what in ((expected, "expected"), (ok, "ok")):
+                if t_ is None:
+                    continue
+                _need_cuda(t_, what)
+                if t_.device.index != self.device:
+                    raise ValueError(f"{what} is on cuda:{t_.device.index}, the batcher on cuda:{self.device}")
+            if ok is None:
+                ok = torch.empty(max(n, 1), dtype=torch.uint8, device=expected.device)
+            if expected.numel() * expected.element_size() != n * self.dsz or ok.numel() * ok.element_size() < n:
+                raise ValueError("expected must hold one digest and ok one byte per chunk")
+            ep, op = expected.data_ptr(), ok.data_ptr()
+        else:
+            expected = np.ascontiguousarray(expected)
+            if expected.nbytes != n * self.dsz:
+                raise ValueError("expected must hold one digest per chunk")
+            if ok is None:
+                ok = np.empty(max(n, 1), dtype=np.uint8)
+            if not (isinstance(ok, np.ndarray) and ok.dtype == np.uint8 and ok.flags.c_contiguous and ok.size >= n):
+                raise ValueError("ok must be a C-contiguous uint8 array of >= n bytes")
+            ep, op = expected.ctypes.data, ok.ctypes.data
+        nbad = np.zeros(1, dtype=np.uint64)
+        check(*self._call("verify_device", P.ctypes.data, L.ctypes.data, n, ep, op, int(on_dev),
+                          *self._producer(after), nbad.ctypes.data, ticket))
+        return n, ok, nbad, (P, L, expected), on_dev
+
+    def verify_device_async(self, ptrs, lens, expected, ok=None, after="current") -> "Batcher.PendingVerify":
+        """md5_batch_verify_device: verify device-resident chunks (ptrs / lens
+        as submit_device_async) under the batcher's kind, compared on the
+        device.  `expected` (and `ok`) as torch tensors on the batcher's
+        device: read and written in place, any alignment -- nothing but the
+        count crosses PCIe; as numpy arrays: host memory, expected copied by
+        the call.  `after` as submit_device_async.  .wait() -> (ok, nbad)."""
+        t = ctypes.c_uint64()
+        n, ok, nbad, keep, on_dev = self._verify_device(ptrs, lens, expected, ok, after, ctypes.byref(t))
+        return Batcher.PendingVerify(self, t.value, n, ok, nbad, None, keep, on_dev)
+
+    def verify_device(self, ptrs, lens, expected, ok=None, after="current"):
+        """The synchronous form of verify_device_async: (ok, nbad)."""
+        n, ok, nbad, _, on_dev = self._verify_device(ptrs, lens, expected, ok, after, None)
+        return (ok if on_dev else ok[:n].astype(bool)), int(nbad[0])
+
     def host_fixed(self, arr: np.ndarray, n: int, length: int, stride: int = None) -> np.ndarray:
         stride = length if stride is None else stride
         a = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
@@ -778,7 +910,9 @@ class Pool(Batcher):
                verify_iov="md5hip_pool_verify_iov", upgrade_iov="md5hip_pool_upgrade_iov",
                host_fixed="md5hip_pool_host_fixed",
                submit_async="md5hip_pool_submit_async", submit_iov_async="md5hip_pool_submit_iov_async",
-               wait="md5hip_pool_wait", poll="md5hip_pool_poll", set_split="md5hip_pool_set_split")
+               wait="md5hip_pool_wait", poll="md5hip_pool_poll", set_split="md5hip_pool_set_split",
+               verify_iov_async="md5hip_pool_verify_iov_async",
+               upgrade_iov_async="md5hip_pool_upgrade_iov_async")
 
     def __init__(self, devices=(0,), slice_bytes: int = 0, nslots: int = 0,
                  kind: int = 0, fastcrc: int = 0):
@@ -824,7 +958,7 @@ class Pool(Batcher):
         raise NotImplementedError("device-resident chunks belong to one device: use a Queue")
 
     submit_device = submit_device_async = submit_device_fixed_async = flush = set_inflight = set_linger = \
-        _unsupported
+        verify_device = verify_device_async = _unsupported
 
 
 def register_host(arr: np.ndarray):
@@ -851,7 +985,7 @@ def pool_plan(lens, nparts: int) -> np.ndarray:
 
 __all__ = ["init_ctx", "update_ctx", "final_ctx", "MD5Context", "MD5Init", "MD5Update", "MD5Final", "MD5_DIGEST_SIZE", "MD5HipError", "arena_empty",
            "plan_desc", "plan_desc_at",
-           "md5", "digest_fixed", "digest_desc", "crc32_fixed", "crc32_desc", "md5crc32_fixed", "md5crc32_desc", "md5crc32_plan",
+           "md5", "digest_fixed", "digest_desc", "digest_compare", "crc32_fixed", "crc32_desc", "md5crc32_fixed", "md5crc32_desc", "md5crc32_plan",
            "MD5CRC32_VARIANTS", "MD5CRC32_FEDSPLIT_MIN_LEN",
            "split_records", "plan_order", "fill_synthetic", "Batcher",
            "Pool", "Queue", "pool_plan", "CRC_VARIANTS", "DESC_VARIANTS",
