@@ -744,6 +744,70 @@ int md5hip_pool_upgrade_iov_async(md5hip_pool *p, const struct md5hip_iov *segs,
                                   unsigned char *ok, unsigned char *md5_out, uint64_t *nbad,
                                   uint64_t *ticket);
 
+/*
+ * Device-resident chunks laid out as page lists, hashed where they lie (ABI
+ * version unchanged: callers find these by symbol).  A netcache block is a
+ * list of fixed-size pages (nc_page_ctrl_t, block.h:143-146); a device tier
+ * that keeps that layout -- an RDMA landing zone carved into pages, a
+ * GPU-side page heap -- holds each block as scattered pages, and the entries
+ * above, which take one address per chunk, would need every block copied
+ * into a contiguous buffer first.
+ *
+ * A paged batch: chunk i has lens[i] bytes; byte k of it is byte
+ * k % page_bytes of the page at device address pages[first[i] + k / page_bytes].
+ * A chunk reads ceil(lens[i] / page_bytes) table entries (it may own more).
+ * page_bytes is a multiple of 128, at most MD5HIP_PAGE_BYTES_MAX.  Pages may
+ * lie anywhere, in any order, and one page may appear in several chunks; only
+ * a chunk's last page may be partly used, and of that page nothing past the
+ * 16-B granule holding the chunk's last byte is read.  Pages on the 16-B
+ * grid are loaded by LDS-DMA like md5hip_digest_desc's chunks (on 128-B
+ * lines: non-temporally); a 64-chunk group holding a page off that grid reads
+ * that page index lane by lane -- correct, slower.
+ *
+ * md5hip_digest_pages: the launcher.  kind: enum md5hip_digest_kind (CRC32:
+ * the whole chunk, no fastcrc window); d_pages, d_first (n entries), d_lens
+ * and the optional d_order (as md5hip_digest_desc: the longest-first order
+ * of md5hip_plan_order) are DEVICE arrays; d_out: n records of 16, 4 or 32
+ * bytes, aligned to 16, 4 and 16.  n == 0: a no-op returning 0.  -EINVAL
+ * before anything is enqueued for an unknown kind, a NULL array, page_bytes
+ * 0, not a multiple of 128 or above the maximum, a misaligned d_out.
+ */
+#define MD5HIP_PAGE_BYTES_MAX (1u << 30)
+int md5hip_digest_pages(int kind, const uint64_t *d_pages, const uint64_t *d_first,
+                        const uint32_t *d_lens, const uint32_t *d_order, uint64_t n,
+                        uint32_t page_bytes, void *d_out, void *stream);
+
+/*
+ * The queue form: `pages` is a HOST array of device addresses on the
+ * batcher's device, page_first a host array of n + 1 entries (chunk i owns
+ * entries [page_first[i], page_first[i+1]) and reads the first
+ * ceil(lens[i] / page_bytes) of them), lens a host array; all three are copied
+ * by the call and reusable on return.  Digests in the batcher's kind (CRC32
+ * with a fastcrc window: -EINVAL), to host or device memory as
+ * md5_batch_submit_device; producer_stream / order as
+ * md5_batch_submit_device_after; ticket NULL = synchronous.  The submission
+ * is cut into slices of at most max_chunks chunks and at most
+ * MD5HIP_PAGES_PER_SLOT(max_chunks) table entries, each slice one launch of
+ * its own on the queue's streams in the longest-first order (several in
+ * flight overlap; they do not coalesce with other submissions).  The page
+ * tables of all slots -- 8 bytes per entry, pinned host and device -- are
+ * allocated by the first such call, once; a batcher that never gets one
+ * allocates nothing for it.
+ * Before anything is enqueued, with *ticket zeroed: -EINVAL for the
+ * page_bytes rules, a page_first that decreases or gives a chunk fewer
+ * entries than its length needs, a NULL page address among those read;
+ * -ENOSYS from a batcher built without md5hip_digest_pages (libmd5hip.so
+ * always has it); -E2BIG for one chunk reading more entries than a slot's
+ * table; -ENOMEM when the tables cannot be had.
+ */
+#define MD5HIP_PAGES_PER_SLOT(max_chunks) \
+    ((uint64_t)(max_chunks) * 4 > 65536 ? (uint64_t)(max_chunks) * 4 : (uint64_t)65536)
+int md5_batch_submit_device_pages(md5hip_batcher *b, const uint64_t *pages,
+                                  const uint64_t *page_first, const uint32_t *lens, uint64_t n,
+                                  uint32_t page_bytes, unsigned char *digests,
+                                  int digests_on_device, void *producer_stream, int order,
+                                  uint64_t *ticket);
+
 #ifdef __cplusplus
 }
 #endif

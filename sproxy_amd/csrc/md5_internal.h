@@ -60,12 +60,15 @@ int md5hip_lines_choice(int variant, uint64_t unlined_bytes, uint64_t bytes);
  * What a submission reads: exactly one of a flat host (ptr, len) list, page
  * lists with per-chunk segment ranges (seg_first has one entry more than
  * the caller has chunks, seg_first[0] = 0), device addresses (no bytes to
- * move), or fixed-length chunks at a fixed stride from one base.  Chunk i of
+ * move), fixed-length chunks at a fixed stride from one base, or
+ * device-resident page lists (a table of page addresses, per-chunk entry
+ * ranges and lengths; page_first has one entry more than the caller has
+ * chunks).  Chunk i of
  * the source is entry first + i of the caller's arrays, so a sub-range of a
  * caller's source is the same arrays with another `first`: nothing is copied
  * or re-based.
  * ------------------------------------------------------------------------ */
-enum md5hip_src_kind { MD5HIP_SRC_PTRS, MD5HIP_SRC_IOV, MD5HIP_SRC_DEVICE, MD5HIP_SRC_FIXED };
+enum md5hip_src_kind { MD5HIP_SRC_PTRS, MD5HIP_SRC_IOV, MD5HIP_SRC_DEVICE, MD5HIP_SRC_FIXED, MD5HIP_SRC_PAGES };
 struct md5hip_src {
     int kind;                            /* enum md5hip_src_kind */
     uint64_t first;
@@ -78,10 +81,28 @@ struct md5hip_src {
     uint32_t len;
     uint64_t stride;
     int base_on_device;                  /* FIXED: device memory, read in place */
+    const uint64_t *pages;               /* PAGES: device addresses; chunk i is lens[i] bytes in the */
+    const uint64_t *page_first;          /* pages at entries page_first[i] .. of `pages`, page_bytes each */
+    uint32_t page_bytes;
 };
 
+/* page_bytes of a paged batch: a multiple of 128 (no 64-B block and no
+ * 128-B stage straddles two pages), at most 2^30 */
+static inline int md5hip_page_bytes_ok(uint32_t page_bytes)
+{
+    return page_bytes != 0 && (page_bytes & 127u) == 0 && page_bytes <= MD5HIP_PAGE_BYTES_MAX;
+}
+
+/* table entries a chunk of len bytes reads */
+static inline uint64_t md5hip_pages_of(uint32_t len, uint32_t page_bytes)
+{
+    return ((uint64_t)len + page_bytes - 1) / page_bytes;
+}
+
 /* 0, or -EINVAL: an array missing, a NULL pointer with a length, a seg_first
- * that does not start at 0 or decreases, len > stride (chunks [0, n)). */
+ * that does not start at 0 or decreases, len > stride, a page size off its
+ * rules, a page_first that decreases or leaves a chunk fewer entries than its
+ * length needs, a NULL page among those (chunks [0, n)). */
 static inline int md5hip_src_check(const struct md5hip_src *s, uint64_t n)
 {
     const uint64_t f = s->first;
@@ -106,6 +127,16 @@ static inline int md5hip_src_check(const struct md5hip_src *s, uint64_t n)
         return 0;
     case MD5HIP_SRC_FIXED:
         return s->base && s->len <= s->stride ? 0 : -EINVAL;
+    case MD5HIP_SRC_PAGES:
+        if (!s->pages || !s->page_first || !s->lens || !md5hip_page_bytes_ok(s->page_bytes)) return -EINVAL;
+        for (uint64_t i = f; i < f + n; i++) {
+            const uint64_t need = md5hip_pages_of(s->lens[i], s->page_bytes);
+            if (s->page_first[i + 1] < s->page_first[i] || s->page_first[i + 1] - s->page_first[i] < need)
+                return -EINVAL;
+            for (uint64_t j = 0; j < need; j++)
+                if (!s->pages[s->page_first[i] + j]) return -EINVAL;
+        }
+        return 0;
     }
     return -EINVAL;
 }
@@ -164,6 +195,15 @@ static inline int md5hip_digest_usable(int kind, uint32_t fastcrc)
     if (kind == MD5HIP_DIGEST_MD5_CRC32 && !md5hip_md5crc32_present()) return -ENOSYS;
     return 0;
 }
+
+/* So is the paged launcher (md5_pages.hip) for the host objects: without it
+ * md5_batch_submit_device_pages returns -ENOSYS before anything is enqueued. */
+#ifndef MD5HIP_DEFINES_PAGES
+extern __typeof__(md5hip_digest_pages) md5hip_digest_pages __attribute__((weak));
+static inline int md5hip_pages_present(void) { return &md5hip_digest_pages != 0; }
+#else
+static inline int md5hip_pages_present(void) { return 1; }
+#endif
 
 /* One range of the digest-compare kernel's table form (md5_verify.hip): for
  * i in [0, count), ok[i] = (bytes [goff, goff + wsz) of record first + i of

@@ -1,0 +1,184 @@
+// md5_pages.hip -- digests of device-resident chunks laid out as page lists
+// (md5hip_digest_pages, include/md5hip.h): a chunk is a run of entries of a
+// page table, each the device address of a page of page_bytes, as netcache
+// keeps a block (nc_page_ctrl_t lists).  The pages are hashed where they lie.
+// A translation unit of its own, linked after md5_kernels.o and md5_verify.o:
+// the hash kernels' code object stays the first gfx950 bundle of the library,
+// byte for byte.
+//
+// The loaders and hashers are md5_kernels.h's.  That header also defines the
+// library's kernels, which md5_kernels.o already holds under their external
+// names: here it is included inside an unnamed namespace, so nothing of it
+// clashes at link time.  The host side of this object emits none of those
+// kernels (unused, internal linkage); its code object carries unreachable
+// copies of the non-template ones, which cost file size and nothing else.
+#define MD5HIP_DEFINES_PAGES   // the launcher is defined here (md5_internal.h)
+#include <errno.h>
+#include <stdint.h>
+
+#include <type_traits>
+#include <utility>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/md5hip.h"
+#include "md5_internal.h"
+
+namespace {
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"   // the kernels this object does not launch
+#include "md5_kernels.h"
+#pragma clang diagnostic pop
+
+using namespace md5hip;
+
+// A paged batch: chunk c = order ? order[i] : i has lens[c] bytes, byte k of
+// it being byte k % page_bytes of the page at pages[first[c] + k / page_bytes].
+struct PageBatch {
+  const uint64_t* __restrict__ pages;
+  const uint64_t* __restrict__ first;
+  const uint32_t* __restrict__ lens;
+  const uint32_t* __restrict__ order;
+  uint32_t page_bytes;                 // a multiple of 128
+};
+
+// pages_group: one wave hashes the 64-chunk group whose first position in
+// `order` is `first` (< n); the hasher is set up by the caller.  The wave
+// walks the page index p up to its largest page count.  Page p of every lane
+// that still has one is a row of an LDS-DMA image (row_set<true>: per-row
+// 64-bit addresses), loaded 128-B stage by stage with the hasher state
+// carried over from page p - 1 (run_stages); lanes whose chunk ended on an
+// earlier page, dead lanes and empty chunks have no stage and alias the
+// wave's longest row.  A page index at which some lane's page is off the
+// 16-B grid is hashed lane-direct instead, each lane its own page.  What is
+// left after a lane's last page -- an odd 64-B block, then len % 64 bytes,
+// both inside that page -- is finished as in desc_xpose_group.
+//
+// A lane reads only the table entries [first[c], first[c] + ceil(len / page_bytes))
+// of its own chunk, and of a page only whole 128-B stages and 64-B blocks
+// that hold chunk bytes, then (load_tail) the 16-B granules up to the one
+// holding the chunk's last byte.
+template <class H>
+__device__ __forceinline__ void pages_group(H& h, const PageBatch& pb, uint64_t n, uint64_t first,
+                                            typename H::Out* __restrict__ out, uint8_t* img) {
+  const uint64_t i = first + (threadIdx.x & 63u);
+  const bool live = i < n;
+  const uint64_t c = live ? (pb.order ? (uint64_t)pb.order[i] : i) : 0;
+  const uint32_t len = live ? pb.lens[c] : 0u;
+  const uint64_t pf = live ? pb.first[c] : 0;
+  const uint32_t P = pb.page_bytes;
+  const uint32_t np = (uint32_t)(((uint64_t)len + P - 1u) / P);   // this lane's pages
+  const uint32_t pmax = wave_max(np);
+  chain_prio(wave_max(len >> 6));
+  typename H::State st = h.init();
+  uint64_t last = 0;                   // this lane's last page
+  uint32_t lastb = 0;                  // and the chunk's bytes in it
+  // the entry of page p is asked for one page ahead, so its round trip runs
+  // under page p - 1's stages
+  uint64_t next = np ? pb.pages[pf] : 0;
+  for (uint32_t p = 0; p < pmax; ++p) {
+    const bool own = p < np;
+    const uint64_t addr = next;
+    next = p + 1u < np ? pb.pages[pf + p + 1u] : 0;
+    const uint64_t rest = own ? (uint64_t)len - (uint64_t)p * P : 0;
+    const uint32_t bytes = rest < P ? (uint32_t)rest : P;          // of the chunk in page p
+    const uint32_t nst = bytes >> 7;                               // whole 128-B stages
+    if (own && p + 1u == np) {
+      last = addr;
+      lastb = bytes;
+    }
+    if (__ballot(own && ((uint32_t)addr & 15u) != 0) != 0) {
+      // some page off the 16-B grid: every lane its own page, the same blocks
+      if (nst) {
+        const uint8_t* page = reinterpret_cast<const uint8_t*>((uintptr_t)addr);
+        if (((uint32_t)addr & 15u) == 0) {
+          ring_range<H, 2, false>(h, st, reinterpret_cast<const uint4*>(page), 2u * nst);
+        } else {
+          for (uint32_t blk = 0; blk < 2u * nst; ++blk) {
+            uint4 w[4];
+            load_block_unaligned(w, page + ((uint64_t)blk << 6));
+            h.block(st, w);
+          }
+        }
+      }
+      continue;
+    }
+    const uint32_t smax = wave_max(nst);
+    if (smax == 0) continue;           // remainders only: finished below
+    // nt only when every row of the page starts on a 128-B line (otherwise a
+    // stage shares a line with the row's next one, which must stay in L2)
+    const bool lined = __ballot(nst != 0 && ((uint32_t)addr & 127u) != 0) == 0;
+    const RowSet rs = row_set<true>(nullptr, addr, nst, smax, img);
+    if (lined) run_stages<2>(h, st, rs);
+    else run_stages<0>(h, st, rs);
+  }
+  if (live) {
+    const uint8_t* page = reinterpret_cast<const uint8_t*>((uintptr_t)last);
+    const uint32_t nfull = lastb >> 6;
+    if (nfull & 1u) {
+      uint4 w[4];
+      const uint8_t* blk = page + ((uint64_t)(nfull - 1u) << 6);
+      if (((uint32_t)last & 15u) == 0) load_block(w, reinterpret_cast<const uint4*>(blk));
+      else load_block_unaligned(w, blk);
+      h.block(st, w);
+    }
+    h.finish(st, page + ((uint64_t)nfull << 6), len & 63u, len);
+    h.store(out, c, st);
+  }
+}
+
+// MD5: one wave per workgroup with its 8 KiB image, held at 4 waves per SIMD
+// by the register file, as md5_desc_xdma.
+__global__ void __launch_bounds__(64)
+md5_pages_xdma(PageBatch pb, uint64_t n, uint4* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint8_t img[8192];
+  asm volatile("" ::: "v127");
+  Md5Hasher<true> h;
+  const uint64_t first = (uint64_t)blockIdx.x * 64u;
+  if (first >= n) return;
+  pages_group(h, pb, n, first, out, img);
+}
+
+// CRC-32 of the whole chunk, and MD5 + CRC-32 in one pass: XDMA16's frame,
+// the 64 KiB tables beside twelve waves' images, one workgroup per CU.
+template <class H>
+__global__ void __launch_bounds__(768)
+pages_xdma16(PageBatch pb, uint64_t n, typename H::Out* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kXdma16Lds<H>];
+  xdma16_frame<H>(lds, n, [&](auto& h, uint64_t first, uint8_t* img) __attribute__((always_inline)) {
+    pages_group(h, pb, n, first, out, img);
+  });
+}
+
+template <typename... P, typename... A>
+int launch(void (*kern)(P...), uint64_t grid, uint32_t block, void* stream, A... args) {
+  hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(block), 0, (hipStream_t)stream, static_cast<P>(args)...);
+  return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+}  // namespace
+
+extern "C" int md5hip_digest_pages(int kind, const uint64_t* d_pages, const uint64_t* d_first,
+                                   const uint32_t* d_lens, const uint32_t* d_order, uint64_t n,
+                                   uint32_t page_bytes, void* d_out, void* stream) {
+  static_assert(sizeof(md5hip_md5crc32) == sizeof(Md5Crc32Record), "record layout");
+  const bool known = kind == MD5HIP_DIGEST_MD5 || kind == MD5HIP_DIGEST_CRC32 || kind == MD5HIP_DIGEST_MD5_CRC32;
+  if (n == 0) return 0;
+  if (!known) return -EINVAL;
+  const uintptr_t align = kind == MD5HIP_DIGEST_CRC32 ? 4 : 16;
+  if (!d_pages || !d_first || !d_lens || !d_out || ((uintptr_t)d_out & (align - 1)) || page_bytes == 0 ||
+      (page_bytes & 127u) || page_bytes > MD5HIP_PAGE_BYTES_MAX)
+    return -EINVAL;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -ENODEV;
+  const uint64_t groups = (n + 63) / 64;
+  if (groups > 0x7fffffffull) return -EINVAL;
+  const PageBatch pb{d_pages, d_first, d_lens, d_order, page_bytes};
+  if (kind == MD5HIP_DIGEST_MD5) return launch(md5_pages_xdma, groups, 64, stream, pb, n, (uint4*)d_out);
+  // one 768-thread workgroup per CU, grid-stride over the groups
+  const uint64_t cus = (uint64_t)md5hip_cu_count();
+  const uint64_t grid = groups < cus ? groups : cus;
+  if (kind == MD5HIP_DIGEST_CRC32)
+    return launch(pages_xdma16<Crc32PermHasher>, grid, 768, stream, pb, n, (uint32_t*)d_out);
+  return launch(pages_xdma16<Md5Crc32Hasher>, grid, 768, stream, pb, n, (Md5Crc32Record*)d_out);
+}

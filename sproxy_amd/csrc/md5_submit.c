@@ -199,7 +199,7 @@ int md5hip_host_unregister(void *base)
  * Slots and tickets
  * ------------------------------------------------------------------------ */
 enum slot_state { SLOT_FREE = 0, SLOT_OPEN, SLOT_INFLIGHT };
-enum slot_mode { MODE_NONE = 0, MODE_STAGED, MODE_ZEROCOPY, MODE_FIXED };
+enum slot_mode { MODE_NONE = 0, MODE_STAGED, MODE_ZEROCOPY, MODE_FIXED, MODE_PAGES };
 
 /* One ticket's chunks in one slot: slot chunks [first, first+count) deliver
  * into `user` (host array, or device memory when on_device). */
@@ -250,6 +250,14 @@ struct slot {
     int fx_dev;
     uint64_t fx_bytes, fx_stride;
     uint32_t fx_len;
+    /* MODE_PAGES (md5_batch_submit_device_pages): one slice of a paged
+     * submission.  Its pg_n table entries are in h_pg, chunk i's from entry
+     * h_off[i] on, its lengths in h_len, its longest-first order (use_order)
+     * in h_ord; h_pg / d_pg are the slot's share of the batcher's page
+     * tables: NULL until the first paged submission (pages_buffers) */
+    uint64_t *h_pg, *d_pg;
+    uint64_t pg_n;
+    uint32_t pg_bytes;
     uint64_t tickets_in;              /* distinct tickets (stats) */
     /* descriptors already on the device / the plan they were ordered by:
      * prepared ahead while another slot's launch runs (slot_prepare) */
@@ -343,6 +351,11 @@ struct md5hip_batcher {
     unsigned char *vb_hin, *vb_din, *vb_hout, *vb_dout;
     uint64_t vin_sz, vout_sz;
     int vready;
+    /* page tables of all slots, allocated by the first paged submission
+     * (pages_buffers): pinned host and device, `pgcap` entries per slot */
+    uint64_t *pb_h, *pb_d;
+    uint64_t pgcap;
+    int pready;
 };
 
 #define CK(x) do { if ((x) != hipSuccess) { rc = -ENODEV; goto fail; } } while (0)
@@ -564,6 +577,10 @@ static int enqueue_kernel(struct slot *sl, unsigned char *dst)
              : sl->kind == MD5HIP_DIGEST_MD5_CRC32
                  ? dual_fixed(src, n, sl->fx_len, sl->fx_stride, (struct md5hip_md5crc32 *)dst, sl->stream)
                  : md5hip_digest_fixed(src, n, sl->fx_len, sl->fx_stride, dst, sl->stream);
+    } else if (sl->mode == MODE_PAGES) {
+        /* the pages are read where they lie, through the tables just sent (enqueue_tables) */
+        rc = md5hip_digest_pages((int)sl->kind, sl->d_pg, sl->d_off, sl->d_len, sl->use_order ? sl->d_ord : NULL, n,
+                                 sl->pg_bytes, dst, sl->stream);
     } else {
         const uint32_t *ord = sl->use_order ? sl->d_ord : NULL;
         const uint64_t *doff = sl->desc_direct ? sl->dh_off : sl->d_off;
@@ -582,6 +599,20 @@ static int enqueue_kernel(struct slot *sl, unsigned char *dst)
     }
     if (rc) return rc;
     return hipEventRecord(sl->kdone, sl->stream) ? -EIO : 0;
+}
+
+/* A paged slot's tables to the device: the page addresses, each chunk's first
+ * entry, the lengths and, when the slice is not longest-first as it came,
+ * the order (the submitter filled the pinned arrays: pages_fill). */
+static int enqueue_tables(struct slot *sl)
+{
+    const uint64_t n = sl->n;
+    if ((sl->pg_n && hipMemcpyAsync(sl->d_pg, sl->h_pg, 8 * sl->pg_n, hipMemcpyHostToDevice, sl->stream)) ||
+        hipMemcpyAsync(sl->d_off, sl->h_off, 8 * n, hipMemcpyHostToDevice, sl->stream) ||
+        hipMemcpyAsync(sl->d_len, sl->h_len, 4 * n, hipMemcpyHostToDevice, sl->stream) ||
+        (sl->use_order && hipMemcpyAsync(sl->d_ord, sl->h_ord, 4 * n, hipMemcpyHostToDevice, sl->stream)))
+        return -EIO;
+    return 0;
 }
 
 /* The slot's verify segments, compared where the digests are (behind kdone,
@@ -687,8 +718,13 @@ static int slot_enqueue(md5hip_batcher *b, struct slot *sl)
         dst = g0->user;
         sl->direct = 1;
     }
-    /* a FIXED slot has no descriptors, and its bytes are in (enqueue_kernel) */
-    if (sl->mode != MODE_FIXED && ((rc = slot_prepare(sl)) || (rc = enqueue_bytes(b, sl)))) return rc;
+    /* a FIXED slot has no descriptors, and its bytes are in (enqueue_kernel);
+     * a PAGES slot has its tables, ordered by its submitter */
+    if (sl->mode == MODE_PAGES) {
+        if ((rc = enqueue_tables(sl))) return rc;
+    } else if (sl->mode != MODE_FIXED && ((rc = slot_prepare(sl)) || (rc = enqueue_bytes(b, sl)))) {
+        return rc;
+    }
     if ((rc = enqueue_kernel(sl, dst))) return rc;
     return enqueue_digests(b, sl);
 }
@@ -703,6 +739,7 @@ static void slot_reset(struct slot *sl)
     sl->urgent = 0;
     sl->inject = 0;
     sl->fx_dev = 0;
+    sl->pg_n = 0;
     sl->mode = MODE_NONE;
     sl->writers = sl->full = sl->flush = sl->err = sl->direct = 0;
     sl->n = sl->used = sl->nseg = sl->ndma = sl->ndsc = 0;
@@ -977,7 +1014,7 @@ static struct slot *slot_open(md5hip_batcher *b, int mode, int kind, uint32_t fa
 static struct slot *slot_for(md5hip_batcher *b, int mode, int kind, uint32_t fastcrc)
 {
     if (b->failed) return NULL;
-    struct slot *sl = (mode == MODE_FIXED ? slot_take : slot_open)(b, mode, kind, fastcrc);
+    struct slot *sl = (mode == MODE_FIXED || mode == MODE_PAGES ? slot_take : slot_open)(b, mode, kind, fastcrc);
     if (!b->failed) return sl;
     slot_try_launch(b, sl);
     return NULL;
@@ -1251,6 +1288,8 @@ static void batcher_free(md5hip_batcher *b)
     if (b->vb_hout) hipHostFree(b->vb_hout);
     if (b->vb_din) hipFree(b->vb_din);
     if (b->vb_dout) hipFree(b->vb_dout);
+    if (b->pb_h) hipHostFree(b->pb_h);
+    if (b->pb_d) hipFree(b->pb_d);
     if (b->after_ev) hipEventDestroy(b->after_ev);
     tk_ring_free(&b->tk);
     pthread_mutex_destroy(&b->mu);
@@ -1301,6 +1340,7 @@ static int batcher_new(int device, uint64_t slice_bytes, uint32_t nslots, uint64
     b->cap = slice_bytes;
     b->maxn = maxn;
     b->segcap = slice_bytes / 1024 < 4096 ? 4096 : slice_bytes / 1024;
+    b->pgcap = MD5HIP_PAGES_PER_SLOT(maxn);
     b->gather = MD5HIP_GATHER_AUTO;
     b->target = nslots > 2 ? 2 : 1;
     b->linger_max_us = 5000;
@@ -2159,6 +2199,137 @@ int md5hip_batch_host_fixed(md5hip_batcher *b, const void *h_base, uint64_t n, u
 {
     const struct md5hip_src src = {.kind = MD5HIP_SRC_FIXED, .base = h_base, .len = len, .stride = stride};
     return enter(b, &src, n, &(struct sub_opt){.digests = digests, .kind = KIND_BATCHER});
+}
+
+/* ------------------------------------------------------------------------
+ * Device-resident page lists (md5hip.h: md5_batch_submit_device_pages)
+ * ------------------------------------------------------------------------ */
+/* The page tables of every slot, allocated once by the first paged
+ * submission (a batcher that never gets one allocates nothing for it): pgcap
+ * entries per slot, pinned host and device.  0, -ENODEV, or -ENOMEM with
+ * nothing allocated. */
+static int pages_buffers(md5hip_batcher *b)
+{
+    if (__atomic_load_n(&b->pready, __ATOMIC_ACQUIRE)) return 0;
+    struct dev_guard g;
+    if (batcher_enter(b, &g)) return -ENODEV;
+    int rc = 0;
+    if (!b->pready) {
+        const uint64_t bytes = 8 * b->pgcap * b->nslots;
+        void *h = NULL, *d = NULL;
+        if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h) hipHostFree(h);
+            rc = -ENOMEM;
+        } else {
+            b->pb_h = h;
+            b->pb_d = d;
+            for (uint32_t k = 0; k < b->nslots; k++) {
+                b->s[k].h_pg = b->pb_h + b->pgcap * k;
+                b->s[k].d_pg = b->pb_d + b->pgcap * k;
+            }
+            __atomic_store_n(&b->pready, 1, __ATOMIC_RELEASE);
+        }
+    }
+    batcher_leave(b, &g);
+    return rc;
+}
+
+/* Chunks [i, i + m) of a paged source into the pinned arrays of slot `sl`,
+ * the submitter's own (outside b->mu): of each chunk the table entries its
+ * length reads, packed, its first entry among them and its length; then the
+ * longest-first order, unless the keys are non-increasing as they came (the
+ * identity then is that order).  0, or the planner's -errno. */
+static int pages_fill(struct slot *sl, const struct md5hip_src *pg, uint64_t i, uint64_t m)
+{
+    const uint32_t *lens = pg->lens + pg->first + i;
+    const uint64_t *pfirst = pg->page_first + pg->first + i;
+    uint64_t at = 0;
+    int sorted = 1;
+    for (uint64_t k = 0; k < m; k++) {
+        const uint64_t need = md5hip_pages_of(lens[k], pg->page_bytes);
+        if (need) memcpy(sl->h_pg + at, pg->pages + pfirst[k], 8 * need);
+        sl->h_off[k] = at;
+        sl->h_len[k] = lens[k];
+        at += need;
+        if (k && (lens[k] >> 6) > (lens[k - 1] >> 6)) sorted = 0;
+    }
+    sl->use_order = !sorted;
+    const int rc = sorted ? 0 : md5hip_plan_desc(sl->h_len, m, sl->h_ord);
+    return rc < 0 ? rc : 0;
+}
+
+/* A paged source, one slot of its own per slice (MODE_PAGES), each slice one
+ * launch: a slice ends at maxn chunks or at pgcap table entries, whichever
+ * comes first (every chunk fits an empty table: the entry checked).
+ * Synchronous when the options name no ticket. */
+static int pages_submit(md5hip_batcher *b, const struct md5hip_src *pg, uint64_t n, const struct sub_opt *o)
+{
+    struct sub s;
+    if (dev_enter(&s.g, b->device)) return -ENODEV;
+    int rc = sub_begin(b, &s, o);
+    if (rc) return rc;
+    for (uint64_t i = 0; i < n && !rc;) {
+        uint64_t m = 0, ents = 0, weight = 0;
+        while (i + m < n && m < b->maxn) {
+            const uint32_t len = pg->lens[pg->first + i + m];
+            const uint64_t need = md5hip_pages_of(len, pg->page_bytes);
+            if (ents + need > b->pgcap) break;
+            ents += need;
+            weight += (uint64_t)len + 64;
+            m++;
+        }
+        struct slot *sl = slot_for(b, MODE_PAGES, s.kind, s.fastcrc);
+        if (!sl) { rc = -ENODEV; break; }
+        sl->n = m;
+        sl->pg_n = ents;
+        sl->pg_bytes = pg->page_bytes;
+        sl->full = 1;
+        load_add(b, sl, weight);                        /* the slot is fresh: load == 0 */
+        if ((rc = seg_push(b, sl, (struct seg){s.t, 0, m, o->digests + (size_t)s.dsz * i, o->on_device}))) {
+            slot_retire(b, sl, rc);
+            break;
+        }
+        slot_after(b, sl, o->after);                    /* the slot is fresh: err == 0 */
+        /* the caller's arrays are copied outside the lock, the slot held by
+         * this writer (as fixed_submit's bytes) */
+        write_begin(b, sl);
+        const int fe = pages_fill(sl, pg, i, m);
+        write_end(b, sl);
+        if (fe && !sl->err) sl->err = fe;
+        slot_try_launch(b, sl);
+        i += m;
+    }
+    return sub_end(b, &s, rc, o->ticket, !o->ticket);
+}
+
+int md5_batch_submit_device_pages(md5hip_batcher *b, const uint64_t *pages, const uint64_t *page_first,
+                                  const uint32_t *lens, uint64_t n, uint32_t page_bytes, unsigned char *digests,
+                                  int digests_on_device, void *producer_stream, int order, uint64_t *ticket)
+{
+    if (ticket) *ticket = 0;
+    if (!b) return -EINVAL;
+    if (n == 0) return 0;
+    if (!digests) return -EINVAL;
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_PAGES, .lens = lens, .pages = pages,
+                                   .page_first = page_first, .page_bytes = page_bytes};
+    int rc = md5hip_src_check(&src, n);
+    if (rc) return rc;
+    /* the batcher's kind at the call, named to the engine (as the verify
+     * entries): whole chunks only, so no CRC-32 window */
+    int kind = MD5HIP_DIGEST_MD5;
+    uint32_t fastcrc = 0;
+    md5hip_batcher_get_digest(b, &kind, &fastcrc);
+    if (fastcrc) return -EINVAL;
+    if (!md5hip_pages_present()) return -ENOSYS;
+    for (uint64_t i = 0; i < n; i++)
+        if (md5hip_pages_of(lens[i], page_bytes) > b->pgcap) return -E2BIG;
+    if ((rc = pages_buffers(b))) return rc;
+    const hipStream_t after = (hipStream_t)producer_stream;
+    return pages_submit(b, &src, n,
+                        &(struct sub_opt){.digests = digests, .on_device = digests_on_device != 0,
+                                          .async = ticket != NULL, .ticket = ticket, .kind = kind,
+                                          .after = order ? &after : NULL});
 }
 
 /* ------------------------------------------------------------------------

@@ -156,6 +156,43 @@ def digest_desc(base, offsets, lens, order=None, out=None, stream=None, variant=
     return out
 
 
+_KIND_DTYPE = {0: (16, torch.uint8 if torch is not None else None),
+               1: (1, torch.int32 if torch is not None else None),
+               2: (32, torch.uint8 if torch is not None else None)}   # enum md5hip_digest_kind: record shape
+
+
+def digest_pages(kind: int, pages, first, lens, page_bytes: int, order=None, out=None, stream=None):
+    """md5hip_digest_pages: digests of chunks laid out as page lists, hashed
+    where the pages lie.  Chunk i is lens[i] bytes; its byte k is byte
+    k % page_bytes of the page at device address pages[first[i] + k // page_bytes].
+    ``pages`` (int64 addresses), ``first`` (int64, n entries) and ``lens``
+    (int32) are device tensors, ``order`` an optional int32 permutation
+    (plan_order's); ``kind`` is Batcher.MD5 / CRC32 / MD5_CRC32, and the result
+    n x 16 uint8, n int32 (the CRCs' bits) or n x 32 uint8 (split_records)."""
+    for t, what in ((pages, "pages"), (first, "first"), (lens, "lens")):
+        _need_cuda(t, what)
+    if pages.dtype != torch.int64 or first.dtype != torch.int64 or lens.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("pages and first must be int64 and lens int32")
+    n = lens.numel()
+    if first.numel() < n:
+        raise ValueError("first has fewer entries than lens")
+    if order is not None:
+        _need_cuda(order, "order")
+        if order.numel() != n or order.dtype not in (torch.int32, torch.uint32):
+            raise ValueError("order must be an int32 permutation of range(n)")
+    if kind not in _KIND_DTYPE:
+        raise ValueError(f"digest kind {kind}")
+    if out is None:
+        width, dt = _KIND_DTYPE[kind]
+        out = torch.empty(n if kind == 1 else (n, width), dtype=dt, device=lens.device)
+    _need_cuda(out, "out")
+    rc = lib().md5hip_digest_pages(kind, pages.data_ptr(), first.data_ptr(), lens.data_ptr(),
+                                   order.data_ptr() if order is not None else None, n, page_bytes,
+                                   out.data_ptr(), _stream(stream))
+    check("md5hip_digest_pages", rc)
+    return out
+
+
 def _ctx_tensor(ctxs):
     _need_cuda(ctxs, "ctxs")
     if ctxs.dtype != torch.uint8 or ctxs.dim() != 2 or ctxs.shape[1] != 88:
@@ -470,6 +507,7 @@ class Batcher:
                submit_device="md5_batch_submit_device", submit_device_on="md5_batch_submit_device_on",
                submit_device_after="md5_batch_submit_device_after",
                submit_device_fixed="md5_batch_submit_device_fixed",
+               submit_device_pages="md5_batch_submit_device_pages",
                set_inflight="md5hip_batcher_set_inflight",
                set_linger="md5hip_batcher_set_linger", set_chain="md5hip_batcher_set_chain",
                stats="md5hip_batcher_get_stats", inject_fault="md5hip_batcher_inject_fault",
@@ -702,6 +740,37 @@ class Batcher:
         check(*self._call("submit_device_fixed", ctypes.c_void_p(addr), n, length, stride, dst, on_dev,
                           *self._producer(after), ctypes.byref(t)))
         return Batcher.Pending(self, t.value, o, n, (base, o), on_dev)
+
+    def _pages(self, pages, page_first, lens, page_bytes, out, after, ticket):
+        """md5_batch_submit_device_pages: host arrays of page addresses on the
+        batcher's device, n + 1 first-entry indices and n lengths (all copied
+        by the call); digests in the batcher's kind into `out`."""
+        P = np.ascontiguousarray(pages, dtype=np.uint64)
+        F = np.ascontiguousarray(page_first, dtype=np.uint64)
+        L = np.ascontiguousarray(lens, dtype=np.uint32)
+        if F.size != L.size + 1:
+            raise ValueError("page_first must have one entry more than lens")
+        if L.size and int(F[-1]) > P.size:
+            raise ValueError("page_first runs past the end of pages")
+        o, on_dev = self._dev_out(L.size, out)
+        dst = o.data_ptr() if on_dev else o.ctypes.data
+        check(*self._call("submit_device_pages", P.ctypes.data, F.ctypes.data, L.ctypes.data, L.size,
+                          page_bytes, dst, on_dev, *self._producer(after), ticket))
+        return o, on_dev, L.size
+
+    def submit_device_pages_async(self, pages, page_first, lens, page_bytes: int, out=None,
+                                  after="current") -> "Batcher.Pending":
+        """Device-resident chunks laid out as page lists, hashed where the
+        pages lie: chunk i is lens[i] bytes in the pages at device addresses
+        pages[page_first[i]], pages[page_first[i] + 1], ... of page_bytes
+        each (a multiple of 128).  `out` and `after` as submit_device_async."""
+        t = ctypes.c_uint64()
+        o, on_dev, n = self._pages(pages, page_first, lens, page_bytes, out, after, ctypes.byref(t))
+        return Batcher.Pending(self, t.value, o, n, (o,), on_dev)
+
+    def submit_device_pages(self, pages, page_first, lens, page_bytes: int, out=None, after="current"):
+        o, on_dev, n = self._pages(pages, page_first, lens, page_bytes, out, after, None)
+        return o if on_dev else self._ret(o, n)
 
     def flush(self):
         check(*self._call("flush"))
@@ -958,7 +1027,7 @@ class Pool(Batcher):
         raise NotImplementedError("device-resident chunks belong to one device: use a Queue")
 
     submit_device = submit_device_async = submit_device_fixed_async = flush = set_inflight = set_linger = \
-        verify_device = verify_device_async = _unsupported
+        verify_device = verify_device_async = submit_device_pages = submit_device_pages_async = _unsupported
 
 
 def register_host(arr: np.ndarray):
