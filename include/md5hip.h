@@ -783,7 +783,8 @@ int md5hip_digest_pages(int kind, const uint64_t *d_pages, const uint64_t *d_fir
  * entries [page_first[i], page_first[i+1]) and reads the first
  * ceil(lens[i] / page_bytes) of them), lens a host array; all three are copied
  * by the call and reusable on return.  Digests in the batcher's kind (CRC32
- * with a fastcrc window: -EINVAL), to host or device memory as
+ * with a fastcrc window: -EINVAL; crc32hip_pages below gives those values), to
+ * host or device memory as
  * md5_batch_submit_device; producer_stream / order as
  * md5_batch_submit_device_after; ticket NULL = synchronous.  The submission
  * is cut into slices of at most max_chunks chunks and at most
@@ -807,6 +808,68 @@ int md5_batch_submit_device_pages(md5hip_batcher *b, const uint64_t *pages,
                                   uint32_t page_bytes, unsigned char *digests,
                                   int digests_on_device, void *producer_stream, int order,
                                   uint64_t *ticket);
+
+/*
+ * fastcrc windows over page lists (blk_make_crc with g__need_fastcrc > 0,
+ * blk_io.c:408-424): crcs[i] = crc32(chunk i) when lens[i] <= fastcrc, else
+ * crc32(its first fastcrc bytes) ^ crc32(its last fastcrc bytes) -- the
+ * values of crc32hip_desc(.., fastcrc, ..) over the same bytes laid
+ * contiguously.  The batch and its rules are md5hip_digest_pages'; fastcrc a
+ * multiple of 4 (else -EINVAL, as crc32hip_fixed); d_crcs: n values, 4-B
+ * aligned.  fastcrc == 0 IS md5hip_digest_pages(MD5HIP_DIGEST_CRC32, ..).
+ * With fastcrc > 0 every window has the same length, so d_order is not read
+ * and the result is the same with or without it.
+ * What is read: of a chunk only the table entries of the pages that hold
+ * window bytes, of those pages only the 16-B granules that hold window bytes
+ * (the pages between a long chunk's two windows are not touched).  A window
+ * may straddle pages (a tail whenever the chunk's last page holds fewer than
+ * fastcrc bytes; both windows when fastcrc > page_bytes) and start at any
+ * byte; such windows, and pages off the 16-B grid, are hashed lane by lane --
+ * correct, slower -- and so is every window when fastcrc is neither 64 nor
+ * 128.  Windows of 64 or 128 bytes inside one page on the 16-B grid (16 KiB
+ * pages, whole blocks: the netcache harness) run pipelined, a 64-row group's
+ * loads under the previous group's lookups.
+ * md5_batch_submit_device_pages still refuses a batcher whose kind has a
+ * fastcrc window: a caller who wants the window CRCs themselves calls this
+ * entry; one who wants them checked, md5_batch_verify_device_pages.
+ */
+int crc32hip_pages(const uint64_t *d_pages, const uint64_t *d_first, const uint32_t *d_lens,
+                   const uint32_t *d_order, uint64_t n, uint32_t page_bytes, uint32_t fastcrc,
+                   uint32_t *d_crcs, void *stream);
+
+/*
+ * Verify and upgrade of paged blocks: md5_batch_submit_device_pages' arrays
+ * and slices (host arrays copied by the call; at most max_chunks chunks and
+ * MD5HIP_PAGES_PER_SLOT entries a slice, each a launch of its own), with
+ * md5_batch_verify_device's expected / ok / on_device / nbad / ticket /
+ * producer_stream / order: *nbad is zeroed by the call and every slice adds
+ * its mismatches into it; ok is in submission order; ticket NULL =
+ * synchronous.  The digests are compared on the device behind each slice's
+ * launch and never leave it (an upgrade's MD5s do: md5_out is host memory,
+ * written for every block, mismatching ones included).
+ * verify: the batcher's digest kind at the call -- MD5, MD5_CRC32 (whole
+ * 32-byte records) or CRC32 with any fastcrc window (the stored value of a
+ * netcache configured with fastcrc; crc32hip_pages computes it).
+ * upgrade: MD5_CRC32 for this call, want_crc against the records' CRC.
+ * Before anything is enqueued, with *ticket zeroed, in this order: -EINVAL
+ * (a NULL array with n > 0, the rules of md5_batch_submit_device_pages);
+ * -ENOSYS from a batcher built without the paged launcher, without the
+ * compare kernel, or -- under a fastcrc window -- without crc32hip_pages
+ * (libmd5hip.so has all three); -E2BIG; -ENOMEM when the page tables or the
+ * verify buffers (each allocated once, by the first call that needs them)
+ * cannot be had.  A launch that fails (-EIO) or never runs (-ENODEV) writes
+ * nothing to host ok, md5_out or nbad.
+ */
+int md5_batch_verify_device_pages(md5hip_batcher *b, const uint64_t *pages,
+                                  const uint64_t *page_first, const uint32_t *lens, uint64_t n,
+                                  uint32_t page_bytes, const void *expected, unsigned char *ok,
+                                  int on_device, void *producer_stream, int order, uint64_t *nbad,
+                                  uint64_t *ticket);
+int md5_batch_upgrade_device_pages(md5hip_batcher *b, const uint64_t *pages,
+                                   const uint64_t *page_first, const uint32_t *lens, uint64_t n,
+                                   uint32_t page_bytes, const uint32_t *want_crc, unsigned char *ok,
+                                   unsigned char *md5_out, void *producer_stream, int order,
+                                   uint64_t *nbad, uint64_t *ticket);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,9 @@ def lib():
         "md5hip_pool_upgrade_iov_async": (i, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
         "md5hip_digest_pages": (i, [i, vp, vp, vp, vp, u64, u32, vp, vp]),
         "md5_batch_submit_device_pages": (i, [vp, vp, vp, vp, u64, u32, vp, i, vp, i, vp]),
+        "crc32hip_pages": (i, [vp, vp, vp, vp, u64, u32, u32, vp, vp]),
+        "md5_batch_verify_device_pages": (i, [vp, vp, vp, vp, u64, u32, vp, vp, i, vp, i, vp, vp]),
+        "md5_batch_upgrade_device_pages": (i, [vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, i, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -216,7 +219,8 @@ EXPORTS = ["MD5Init", "MD5Update", "MD5Final", "nc_MD5Init", "nc_MD5Update", "nc
            "md5crc32hip_plan", "md5crc32hip_fixed_variant", "md5crc32hip_desc_variant",
            "md5hip_digest_compare", "md5hip_batch_verify_iov_async", "md5hip_batch_upgrade_iov_async",
            "md5_batch_verify_device", "md5hip_pool_verify_iov_async", "md5hip_pool_upgrade_iov_async",
-           "md5hip_digest_pages", "md5_batch_submit_device_pages"]
+           "md5hip_digest_pages", "md5_batch_submit_device_pages", "crc32hip_pages",
+           "md5_batch_verify_device_pages", "md5_batch_upgrade_device_pages"]
 
 
 def check(fn, rc):

@@ -201,8 +201,13 @@ static inline int md5hip_digest_usable(int kind, uint32_t fastcrc)
 #ifndef MD5HIP_DEFINES_PAGES
 extern __typeof__(md5hip_digest_pages) md5hip_digest_pages __attribute__((weak));
 static inline int md5hip_pages_present(void) { return &md5hip_digest_pages != 0; }
+/* and the fastcrc windows over page lists, which a paged verify under a
+ * CRC-32 window launches: -ENOSYS for that kind alone without it */
+extern __typeof__(crc32hip_pages) crc32hip_pages __attribute__((weak));
+static inline int md5hip_pages_fast_present(void) { return &crc32hip_pages != 0; }
 #else
 static inline int md5hip_pages_present(void) { return 1; }
+static inline int md5hip_pages_fast_present(void) { return 1; }
 #endif
 
 /* One range of the digest-compare kernel's table form (md5_verify.hip): for

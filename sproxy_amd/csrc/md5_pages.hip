@@ -2,6 +2,8 @@
 // (md5hip_digest_pages, include/md5hip.h): a chunk is a run of entries of a
 // page table, each the device address of a page of page_bytes, as netcache
 // keeps a block (nc_page_ctrl_t lists).  The pages are hashed where they lie.
+// Also blk_make_crc's fastcrc windows over such lists (crc32hip_pages), of
+// which only the windows' bytes are read.
 // A translation unit of its own, linked after md5_kernels.o and md5_verify.o:
 // the hash kernels' code object stays the first gfx950 bundle of the library,
 // byte for byte.
@@ -150,6 +152,156 @@ pages_xdma16(PageBatch pb, uint64_t n, typename H::Out* __restrict__ out) {
   });
 }
 
+// ---------------------------------------------------------------------------
+// blk_make_crc's fastcrc windows (blk_io.c:408-424) over page lists
+// (crc32hip_pages): crcs[k] = CRC(first F bytes) ^ CRC(last F bytes) of chunk
+// k, the whole chunk's CRC when it has at most F bytes.  The rows are
+// FastWindows': row 2k = chunk k's head window, row 2k + 1 its tail window
+// (empty for a chunk of <= F bytes: CRC 0, the XOR identity), lanes 2k and
+// 2k + 1 combine.  crc32_fast_pipe's frame: the perm tables alone in LDS,
+// sixteen waves per CU, persistent, groups wave-major; the next group's
+// windows are loaded into VGPRs before the current group is hashed.
+// ---------------------------------------------------------------------------
+// A lane's window: `len` bytes from `at`, which lies `room` bytes before the
+// end of its page, entry `ent` of the table; what does not fit goes on at
+// byte 0 of entries ent + 1, ...  Neither `at` nor `ent` means anything when
+// len == 0, and no table entry is read for such a row.
+struct PageWin {
+  const uint8_t* at;
+  uint64_t ent;
+  uint32_t room, len;
+  bool live;
+  bool pipe;           // wave-uniform: every live row is F bytes inside one page on the 16-B grid
+};
+
+__device__ __forceinline__ PageWin page_window(const PageBatch& pb, uint64_t rows, uint64_t gi, uint32_t F,
+                                               bool pipeF) {
+  PageWin w;
+  const uint64_t i = gi * 64u + (threadIdx.x & 63u);
+  w.live = i < rows;
+  const uint64_t k = i >> 1;
+  const uint32_t L = w.live ? pb.lens[k] : 0u;
+  const bool tail = (i & 1u) != 0;
+  w.len = L <= F ? (tail ? 0u : L) : F;
+  const uint32_t start = tail && L > F ? L - F : 0u;     // the window's first byte in its chunk
+  const uint32_t P = pb.page_bytes;
+  const uint32_t e = start / P, q = start - e * P;
+  w.room = P - q;
+  w.ent = 0;
+  uint64_t addr = 0;
+  if (w.len) {
+    w.ent = pb.first[k] + e;
+    addr = pb.pages[w.ent] + q;
+  }
+  const bool simple = !w.live || (w.len == F && F <= w.room && ((uint32_t)addr & 15u) == 0);
+  w.pipe = pipeF && __ballot(!simple) == 0;
+  // dead lanes of a pipelined group load the group's first window (row 0 is
+  // live, and simple there)
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)addr, 0, 64);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(addr >> 32), 0, 64);
+  if (!w.live) addr = ((uint64_t)hi << 32) | lo;
+  w.at = reinterpret_cast<const uint8_t*>((uintptr_t)addr);
+  return w;
+}
+
+// A window of any shape by its own lane: page by page, each piece hashed and
+// finished by lane_range (any alignment; of a piece only the 64-B blocks, and
+// then the 16-B or 4-B granules, that hold its bytes are read).  CRC-32 runs
+// over a byte stream, so a piece may end anywhere: finish's complement is
+// taken back, and the raw register goes on into the next page.
+__device__ __forceinline__ void page_window_lane(Crc32PermHasher& h, Crc32State& st, const PageBatch& pb,
+                                                 const PageWin& w) {
+  const uint8_t* p = w.at;
+  uint64_t ent = w.ent;
+  uint32_t left = w.len, room = w.room;
+  for (;;) {
+    const uint32_t piece = left < room ? left : room;
+    lane_range<Crc32PermHasher, 2>(h, st, p, piece);
+    left -= piece;
+    if (left == 0) break;
+    st.c = ~st.c;
+    p = reinterpret_cast<const uint8_t*>((uintptr_t)pb.pages[++ent]);
+    room = pb.page_bytes;
+  }
+}
+
+// The ring of loaded groups is fast_pipe_body's, written out here: that body
+// hashes FastWindows rows, one address each, where a row of a paged batch may
+// be several pieces, and it stays as md5_kernels.o compiled it.
+__global__ void __launch_bounds__(1024)
+crc32_pages_fast(PageBatch pb, uint64_t n, uint32_t F, uint32_t* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[Crc32PermHasher::kLdsBytes];
+  constexpr int D = 2;                                    // window groups in flight per wave
+  Crc32PermHasher h;
+  h.setup(lds);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t rows = 2 * n;
+  const uint64_t ngroups = (rows + 63) / 64;
+  const uint64_t step = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const bool pipeF = F == 64u || F == 128u;               // windows of one or two whole blocks
+  const uint32_t nb = F >> 6;
+  auto fetch = [&](const PageWin& w, uint4 (&W)[2][4]) __attribute__((always_inline)) {
+    const uint4* q = reinterpret_cast<const uint4*>(w.at);
+    if (nb == 2) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {      // a line's halves in alternating instructions (fast_pipe_body)
+        W[0][k] = ld16(q + k);
+        __builtin_amdgcn_sched_barrier(0);
+        W[1][k] = ld16(q + 4 + k);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      load_block(W[0], q);
+    }
+  };
+  auto hash = [&](const PageWin& w, uint64_t gi, uint4 (&W)[2][4]) __attribute__((always_inline)) {
+    Crc32State st = h.init();
+    if (w.pipe) {
+      h.block(st, W[0]);
+      if (nb == 2) h.block(st, W[1]);
+      h.finish(st, w.at, 0u, F);
+    } else if (w.live) {
+      // placed again: a window's table entry and room in its page are not
+      // kept in flight beside the loaded group (VGPRs: 128 at 16 waves per CU)
+      page_window_lane(h, st, pb, page_window(pb, rows, gi, F, pipeF));
+    }
+    if (w.live) {                        // pairs are live together
+      const uint64_t i = gi * 64u + (threadIdx.x & 63u);
+      const uint32_t v = st.c ^ (uint32_t)__shfl_xor((int)st.c, 1, 64);
+      if (!(i & 1u)) out[i >> 1] = v;
+    }
+  };
+  uint64_t g0 = (uint64_t)wave * gridDim.x + blockIdx.x;
+  if (g0 >= ngroups) return;
+  uint4 buf[D][2][4];
+  PageWin win[D];
+#pragma unroll
+  for (int j = 0; j < D - 1; ++j) {
+    const uint64_t g = g0 + (uint64_t)j * step;
+    win[j] = PageWin{};
+    if (g < ngroups) {
+      win[j] = page_window(pb, rows, g, F, pipeF);
+      if (win[j].pipe) fetch(win[j], buf[j]);
+    }
+  }
+  for (;;) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      const int pj = (j + D - 1) % D;                   // the slot freed one group ago
+      const uint64_t gp = g0 + (uint64_t)(j + D - 1) * step;
+      win[pj] = PageWin{};
+      if (gp < ngroups) {
+        win[pj] = page_window(pb, rows, gp, F, pipeF);
+        if (win[pj].pipe) fetch(win[pj], buf[pj]);
+      }
+      const uint64_t g = g0 + (uint64_t)j * step;
+      if (g < ngroups) hash(win[j], g, buf[j]);
+    }
+    g0 += (uint64_t)D * step;
+    if (g0 >= ngroups) break;
+  }
+}
+
 template <typename... P, typename... A>
 int launch(void (*kern)(P...), uint64_t grid, uint32_t block, void* stream, A... args) {
   hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(block), 0, (hipStream_t)stream, static_cast<P>(args)...);
@@ -181,4 +333,25 @@ extern "C" int md5hip_digest_pages(int kind, const uint64_t* d_pages, const uint
   if (kind == MD5HIP_DIGEST_CRC32)
     return launch(pages_xdma16<Crc32PermHasher>, grid, 768, stream, pb, n, (uint32_t*)d_out);
   return launch(pages_xdma16<Md5Crc32Hasher>, grid, 768, stream, pb, n, (Md5Crc32Record*)d_out);
+}
+
+extern "C" int crc32hip_pages(const uint64_t* d_pages, const uint64_t* d_first, const uint32_t* d_lens,
+                              const uint32_t* d_order, uint64_t n, uint32_t page_bytes, uint32_t fastcrc,
+                              uint32_t* d_crcs, void* stream) {
+  // whole chunks: the paged CRC-32 kernel itself
+  if (fastcrc == 0)
+    return md5hip_digest_pages(MD5HIP_DIGEST_CRC32, d_pages, d_first, d_lens, d_order, n, page_bytes, d_crcs, stream);
+  if (n == 0) return 0;
+  if (!d_pages || !d_first || !d_lens || !d_crcs || ((uintptr_t)d_crcs & 3u) || (fastcrc & 3u) || page_bytes == 0 ||
+      (page_bytes & 127u) || page_bytes > MD5HIP_PAGE_BYTES_MAX)
+    return -EINVAL;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -ENODEV;
+  const uint64_t groups = (n + 31) / 32;                 // 64 window rows each
+  if (groups > 0x7fffffffull) return -EINVAL;
+  // every window is fastcrc bytes (or the whole of a shorter chunk) whatever
+  // the order, and crcs[k] is chunk k's: d_order changes nothing, and is not read
+  const PageBatch pb{d_pages, d_first, d_lens, nullptr, page_bytes};
+  const uint64_t cus = (uint64_t)md5hip_cu_count();
+  return launch(crc32_pages_fast, groups < cus ? groups : cus, 1024, stream, pb, n, fastcrc, d_crcs);
 }

@@ -578,9 +578,14 @@ static int enqueue_kernel(struct slot *sl, unsigned char *dst)
                  ? dual_fixed(src, n, sl->fx_len, sl->fx_stride, (struct md5hip_md5crc32 *)dst, sl->stream)
                  : md5hip_digest_fixed(src, n, sl->fx_len, sl->fx_stride, dst, sl->stream);
     } else if (sl->mode == MODE_PAGES) {
-        /* the pages are read where they lie, through the tables just sent (enqueue_tables) */
-        rc = md5hip_digest_pages((int)sl->kind, sl->d_pg, sl->d_off, sl->d_len, sl->use_order ? sl->d_ord : NULL, n,
-                                 sl->pg_bytes, dst, sl->stream);
+        /* the pages are read where they lie, through the tables just sent
+         * (enqueue_tables); under a fastcrc window (a paged verify: the submit
+         * entry refuses one) only the windows' granules */
+        const uint32_t *ord = sl->use_order ? sl->d_ord : NULL;
+        rc = sl->fastcrc ? crc32hip_pages(sl->d_pg, sl->d_off, sl->d_len, ord, n, sl->pg_bytes, sl->fastcrc,
+                                          (uint32_t *)dst, sl->stream)
+                         : md5hip_digest_pages((int)sl->kind, sl->d_pg, sl->d_off, sl->d_len, ord, n, sl->pg_bytes,
+                                               dst, sl->stream);
     } else {
         const uint32_t *ord = sl->use_order ? sl->d_ord : NULL;
         const uint64_t *doff = sl->desc_direct ? sl->dh_off : sl->d_off;
@@ -2262,7 +2267,8 @@ static int pages_fill(struct slot *sl, const struct md5hip_src *pg, uint64_t i, 
 /* A paged source, one slot of its own per slice (MODE_PAGES), each slice one
  * launch: a slice ends at maxn chunks or at pgcap table entries, whichever
  * comes first (every chunk fits an empty table: the entry checked).
- * Synchronous when the options name no ticket. */
+ * Synchronous when the options name no ticket.  With o->verify every slice
+ * is one verify segment (the entry made sure of verify_buffers). */
 static int pages_submit(md5hip_batcher *b, const struct md5hip_src *pg, uint64_t n, const struct sub_opt *o)
 {
     struct sub s;
@@ -2286,7 +2292,9 @@ static int pages_submit(md5hip_batcher *b, const struct md5hip_src *pg, uint64_t
         sl->pg_bytes = pg->page_bytes;
         sl->full = 1;
         load_add(b, sl, weight);                        /* the slot is fresh: load == 0 */
-        if ((rc = seg_push(b, sl, (struct seg){s.t, 0, m, o->digests + (size_t)s.dsz * i, o->on_device}))) {
+        struct seg sg = {s.t, 0, m, o->verify ? NULL : o->digests + (size_t)s.dsz * i, o->on_device};
+        if (o->verify) seg_verify(sl, &sg, o->verify, i);
+        if ((rc = seg_push(b, sl, sg))) {
             slot_retire(b, sl, rc);
             break;
         }
@@ -2564,4 +2572,69 @@ int md5_batch_verify_device(md5hip_batcher *b, const uint64_t *d_ptrs, const uin
                         &(struct md5hip_verify_opt){.expected = expected, .ok = ok, .nbad = nbad,
                                                     .wsz = md5hip_digest_size(kind), .on_device = on_device != 0},
                         ticket != NULL, ticket, order ? &after : NULL);
+}
+
+/* What both paged verify entries do once they have named what is compared
+ * (n > 0): the checks in the order in which the errors win (arguments and
+ * page rules -- before the batcher is touched --, the launchers, one chunk
+ * against a slot's table, the buffers), then the paged engine with verify
+ * segments.  kind KIND_BATCHER: the batcher's kind and window at the call,
+ * whole digests compared (v->wsz is set here). */
+static int enter_verify_pages(md5hip_batcher *b, const struct md5hip_src *src, uint64_t n, int kind,
+                              struct md5hip_verify_opt *v, void *producer_stream, int order, uint64_t *ticket)
+{
+    int rc;
+    uint32_t fastcrc = 0;
+    if (!v->expected || !v->ok || (v->md5_out && v->on_device)) return -EINVAL;
+    if ((rc = md5hip_src_check(src, n))) return rc;
+    if (kind == KIND_BATCHER) {
+        md5hip_batcher_get_digest(b, &kind, &fastcrc);
+        v->wsz = md5hip_digest_size(kind);
+    }
+    if ((rc = md5hip_digest_usable(kind, fastcrc))) return rc;
+    if (!md5hip_pages_present() || !md5hip_compare_present() || (fastcrc && !md5hip_pages_fast_present()))
+        return -ENOSYS;
+    for (uint64_t i = 0; i < n; i++)
+        if (md5hip_pages_of(src->lens[i], src->page_bytes) > b->pgcap) return -E2BIG;
+    if ((rc = pages_buffers(b)) || (rc = verify_buffers(b))) return rc;
+    const hipStream_t after = (hipStream_t)producer_stream;
+    return pages_submit(b, src, n,
+                        &(struct sub_opt){.on_device = v->on_device, .async = ticket != NULL, .ticket = ticket,
+                                          .kind = kind, .fastcrc = fastcrc, .after = order ? &after : NULL,
+                                          .verify = v});
+}
+
+int md5_batch_verify_device_pages(md5hip_batcher *b, const uint64_t *pages, const uint64_t *page_first,
+                                  const uint32_t *lens, uint64_t n, uint32_t page_bytes, const void *expected,
+                                  unsigned char *ok, int on_device, void *producer_stream, int order, uint64_t *nbad,
+                                  uint64_t *ticket)
+{
+    if (ticket) *ticket = 0;
+    if (!b) return -EINVAL;
+    if (nbad) *nbad = 0;
+    if (n == 0) return 0;
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_PAGES, .lens = lens, .pages = pages,
+                                   .page_first = page_first, .page_bytes = page_bytes};
+    return enter_verify_pages(b, &src, n, KIND_BATCHER,
+                              &(struct md5hip_verify_opt){.expected = expected, .ok = ok, .nbad = nbad,
+                                                          .on_device = on_device != 0},
+                              producer_stream, order, ticket);
+}
+
+int md5_batch_upgrade_device_pages(md5hip_batcher *b, const uint64_t *pages, const uint64_t *page_first,
+                                   const uint32_t *lens, uint64_t n, uint32_t page_bytes, const uint32_t *want_crc,
+                                   unsigned char *ok, unsigned char *md5_out, void *producer_stream, int order,
+                                   uint64_t *nbad, uint64_t *ticket)
+{
+    if (ticket) *ticket = 0;
+    if (!b) return -EINVAL;
+    if (nbad) *nbad = 0;
+    if (n == 0) return 0;
+    if (!md5_out) return -EINVAL;
+    const struct md5hip_src src = {.kind = MD5HIP_SRC_PAGES, .lens = lens, .pages = pages,
+                                   .page_first = page_first, .page_bytes = page_bytes};
+    return enter_verify_pages(b, &src, n, MD5HIP_DIGEST_MD5_CRC32,
+                              &(struct md5hip_verify_opt){.expected = want_crc, .ok = ok, .md5_out = md5_out,
+                                                          .nbad = nbad, .goff = 16, .wsz = 4},
+                              producer_stream, order, ticket);
 }

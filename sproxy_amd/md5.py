@@ -193,6 +193,36 @@ def digest_pages(kind: int, pages, first, lens, page_bytes: int, order=None, out
     return out
 
 
+def crc32_pages(pages, first, lens, page_bytes: int, fastcrc: int, order=None, out=None, stream=None):
+    """crc32hip_pages: blk_make_crc's values of chunks laid out as page lists
+    (digest_pages' arrays) -- crc32(chunk) for a chunk of at most ``fastcrc``
+    bytes, else crc32(first fastcrc bytes) ^ crc32(last fastcrc bytes); only
+    the windows are read.  fastcrc == 0: digest_pages(Batcher.CRC32, ...).
+    Returns n int32 (the CRCs' bits); ``order`` changes nothing once
+    fastcrc > 0."""
+    if fastcrc == 0:
+        return digest_pages(1, pages, first, lens, page_bytes, order=order, out=out, stream=stream)
+    for t, what in ((pages, "pages"), (first, "first"), (lens, "lens")):
+        _need_cuda(t, what)
+    if pages.dtype != torch.int64 or first.dtype != torch.int64 or lens.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("pages and first must be int64 and lens int32")
+    n = lens.numel()
+    if first.numel() < n:
+        raise ValueError("first has fewer entries than lens")
+    if order is not None:
+        _need_cuda(order, "order")
+        if order.numel() != n or order.dtype not in (torch.int32, torch.uint32):
+            raise ValueError("order must be an int32 permutation of range(n)")
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=lens.device)
+    _need_cuda(out, "out")
+    rc = lib().crc32hip_pages(pages.data_ptr(), first.data_ptr(), lens.data_ptr(),
+                              order.data_ptr() if order is not None else None, n, page_bytes, fastcrc,
+                              out.data_ptr(), _stream(stream))
+    check("crc32hip_pages", rc)
+    return out
+
+
 def _ctx_tensor(ctxs):
     _need_cuda(ctxs, "ctxs")
     if ctxs.dtype != torch.uint8 or ctxs.dim() != 2 or ctxs.shape[1] != 88:
@@ -508,6 +538,8 @@ class Batcher:
                submit_device_after="md5_batch_submit_device_after",
                submit_device_fixed="md5_batch_submit_device_fixed",
                submit_device_pages="md5_batch_submit_device_pages",
+               verify_device_pages="md5_batch_verify_device_pages",
+               upgrade_device_pages="md5_batch_upgrade_device_pages",
                set_inflight="md5hip_batcher_set_inflight",
                set_linger="md5hip_batcher_set_linger", set_chain="md5hip_batcher_set_chain",
                stats="md5hip_batcher_get_stats", inject_fault="md5hip_batcher_inject_fault",
@@ -745,13 +777,7 @@ class Batcher:
         """md5_batch_submit_device_pages: host arrays of page addresses on the
         batcher's device, n + 1 first-entry indices and n lengths (all copied
         by the call); digests in the batcher's kind into `out`."""
-        P = np.ascontiguousarray(pages, dtype=np.uint64)
-        F = np.ascontiguousarray(page_first, dtype=np.uint64)
-        L = np.ascontiguousarray(lens, dtype=np.uint32)
-        if F.size != L.size + 1:
-            raise ValueError("page_first must have one entry more than lens")
-        if L.size and int(F[-1]) > P.size:
-            raise ValueError("page_first runs past the end of pages")
+        P, F, L = self._page_arrays(pages, page_first, lens)
         o, on_dev = self._dev_out(L.size, out)
         dst = o.data_ptr() if on_dev else o.ctypes.data
         check(*self._call("submit_device_pages", P.ctypes.data, F.ctypes.data, L.ctypes.data, L.size,
@@ -894,7 +920,16 @@ class Batcher:
         L = np.ascontiguousarray(lens, dtype=np.uint32)
         if P.size != L.size:
             raise ValueError("ptrs and lens differ in length")
-        n = P.size
+        n, ok, ep, op, on_dev, expected = self._verify_where(P.size, expected, ok)
+        nbad = np.zeros(1, dtype=np.uint64)
+        check(*self._call("verify_device", P.ctypes.data, L.ctypes.data, n, ep, op, int(on_dev),
+                          *self._producer(after), nbad.ctypes.data, ticket))
+        return n, ok, nbad, (P, L, expected), on_dev
+
+    def _verify_where(self, n, expected, ok):
+        """The expected values and ok bytes of a device verify, both torch
+        tensors on the batcher's device or both numpy arrays: (n, ok, their
+        addresses, on_device, expected as passed down)."""
         on_dev = torch is not None and isinstance(expected, torch.Tensor)
         if on_dev:
             for t_, what in ((expected, "expected"), (ok, "ok")):
@@ -917,10 +952,7 @@ class Batcher:
             if not (isinstance(ok, np.ndarray) and ok.dtype == np.uint8 and ok.flags.c_contiguous and ok.size >= n):
                 raise ValueError("ok must be a C-contiguous uint8 array of >= n bytes")
             ep, op = expected.ctypes.data, ok.ctypes.data
-        nbad = np.zeros(1, dtype=np.uint64)
-        check(*self._call("verify_device", P.ctypes.data, L.ctypes.data, n, ep, op, int(on_dev),
-                          *self._producer(after), nbad.ctypes.data, ticket))
-        return n, ok, nbad, (P, L, expected), on_dev
+        return n, ok, ep, op, on_dev, expected
 
     def verify_device_async(self, ptrs, lens, expected, ok=None, after="current") -> "Batcher.PendingVerify":
         """md5_batch_verify_device: verify device-resident chunks (ptrs / lens
@@ -937,6 +969,70 @@ class Batcher:
         """The synchronous form of verify_device_async: (ok, nbad)."""
         n, ok, nbad, _, on_dev = self._verify_device(ptrs, lens, expected, ok, after, None)
         return (ok if on_dev else ok[:n].astype(bool)), int(nbad[0])
+
+    def _page_arrays(self, pages, page_first, lens):
+        P = np.ascontiguousarray(pages, dtype=np.uint64)
+        F = np.ascontiguousarray(page_first, dtype=np.uint64)
+        L = np.ascontiguousarray(lens, dtype=np.uint32)
+        if F.size != L.size + 1:
+            raise ValueError("page_first must have one entry more than lens")
+        if L.size and int(F[-1]) > P.size:
+            raise ValueError("page_first runs past the end of pages")
+        return P, F, L
+
+    def _verify_pages(self, pages, page_first, lens, page_bytes, expected, ok, after, ticket):
+        P, F, L = self._page_arrays(pages, page_first, lens)
+        n, ok, ep, op, on_dev, expected = self._verify_where(L.size, expected, ok)
+        nbad = np.zeros(1, dtype=np.uint64)
+        check(*self._call("verify_device_pages", P.ctypes.data, F.ctypes.data, L.ctypes.data, n, page_bytes, ep, op,
+                          int(on_dev), *self._producer(after), nbad.ctypes.data, ticket))
+        return n, ok, nbad, (expected,), on_dev
+
+    def verify_device_pages_async(self, pages, page_first, lens, page_bytes: int, expected, ok=None,
+                                  after="current") -> "Batcher.PendingVerify":
+        """md5_batch_verify_device_pages: verify blocks laid out as page lists
+        (submit_device_pages_async's arrays) under the batcher's kind -- MD5,
+        MD5_CRC32 or CRC32 with any fastcrc window -- compared on the device.
+        `expected`, `ok` and `after` as verify_device_async.  .wait() ->
+        (ok, nbad)."""
+        t = ctypes.c_uint64()
+        n, ok, nbad, keep, on_dev = self._verify_pages(pages, page_first, lens, page_bytes, expected, ok, after,
+                                                       ctypes.byref(t))
+        return Batcher.PendingVerify(self, t.value, n, ok, nbad, None, keep, on_dev)
+
+    def verify_device_pages(self, pages, page_first, lens, page_bytes: int, expected, ok=None, after="current"):
+        """The synchronous form of verify_device_pages_async: (ok, nbad)."""
+        n, ok, nbad, _, on_dev = self._verify_pages(pages, page_first, lens, page_bytes, expected, ok, after, None)
+        return (ok if on_dev else ok[:n].astype(bool)), int(nbad[0])
+
+    def _upgrade_pages(self, pages, page_first, lens, page_bytes, want_crc, after, ticket):
+        P, F, L = self._page_arrays(pages, page_first, lens)
+        n = L.size
+        want = np.ascontiguousarray(want_crc, dtype=np.uint32)
+        if want.size != n:
+            raise ValueError("want_crc must hold one CRC-32 per chunk")
+        ok = np.empty(max(n, 1), dtype=np.uint8)
+        md5s = np.empty((max(n, 1), 16), dtype=np.uint8)
+        nbad = np.zeros(1, dtype=np.uint64)
+        check(*self._call("upgrade_device_pages", P.ctypes.data, F.ctypes.data, L.ctypes.data, n, page_bytes,
+                          want.ctypes.data, ok.ctypes.data, md5s.ctypes.data, *self._producer(after),
+                          nbad.ctypes.data, ticket))
+        return n, ok, md5s, nbad
+
+    def upgrade_device_pages_async(self, pages, page_first, lens, page_bytes: int, want_crc,
+                                   after="current") -> "Batcher.PendingVerify":
+        """md5_batch_upgrade_device_pages: one MD5_CRC32 pass over paged
+        blocks whatever kind is set; .wait() -> (ok, md5, nbad), ok[i] =
+        crc32(block i) == want_crc[i] compared on the device, and the MD5 of
+        every block."""
+        t = ctypes.c_uint64()
+        n, ok, md5s, nbad = self._upgrade_pages(pages, page_first, lens, page_bytes, want_crc, after, ctypes.byref(t))
+        return Batcher.PendingVerify(self, t.value, n, ok, nbad, md5s, ())
+
+    def upgrade_device_pages(self, pages, page_first, lens, page_bytes: int, want_crc, after="current"):
+        """The synchronous form of upgrade_device_pages_async: (ok, md5, nbad)."""
+        n, ok, md5s, nbad = self._upgrade_pages(pages, page_first, lens, page_bytes, want_crc, after, None)
+        return ok[:n].astype(bool), md5s[:n], int(nbad[0])
 
     def host_fixed(self, arr: np.ndarray, n: int, length: int, stride: int = None) -> np.ndarray:
         stride = length if stride is None else stride
@@ -1027,7 +1123,9 @@ class Pool(Batcher):
         raise NotImplementedError("device-resident chunks belong to one device: use a Queue")
 
     submit_device = submit_device_async = submit_device_fixed_async = flush = set_inflight = set_linger = \
-        verify_device = verify_device_async = submit_device_pages = submit_device_pages_async = _unsupported
+        verify_device = verify_device_async = submit_device_pages = submit_device_pages_async = \
+        verify_device_pages = verify_device_pages_async = upgrade_device_pages = upgrade_device_pages_async = \
+        _unsupported
 
 
 def register_host(arr: np.ndarray):
