@@ -871,6 +871,48 @@ int md5_batch_upgrade_device_pages(md5hip_batcher *b, const uint64_t *pages,
                                    unsigned char *md5_out, void *producer_stream, int order,
                                    uint64_t *nbad, uint64_t *ticket);
 
+/*
+ * MD5Update on caller-owned contexts over page lists: the paged form of
+ * md5hip_update_ctx, for objects that arrive block by block into a tier that
+ * keeps its blocks as pages.  Context i ends byte for byte -- buf, bits with
+ * the carry into bits[1] and len >> 29, in[] with the tail in its first bytes
+ * and past them the last block compressed, or its old bytes if none was -- as
+ * MD5Update(ctx i, B_i, d_lens[i]) leaves it (md5.c:169-215), B_i being chunk
+ * i of the paged batch d_pages / d_first / d_lens / page_bytes exactly as
+ * md5hip_digest_pages defines it; the update starts at byte 0 of the chunk's
+ * first page.  d_lens[i] == 0 leaves context i untouched.  There is no
+ * d_order: a context's index is its lane, as in md5hip_update_ctx.
+ * Asynchronous on `stream`; calls on one stream apply in order.  n == 0: a
+ * no-op returning 0.  -EINVAL before anything is enqueued, and before the
+ * device is looked at, for a NULL array, d_ctxs not 4-byte aligned, page_bytes
+ * 0, not a multiple of 128 or above MD5HIP_PAGE_BYTES_MAX, more than 2^31 - 1
+ * groups of 64 contexts; -ENODEV / -EIO as elsewhere.
+ * What is read is md5hip_digest_pages': of chunk i the table entries
+ * [d_first[i], d_first[i] + ceil(len / page_bytes)) alone (one of them twice
+ * when the last page holds under 64 bytes), of its last page nothing past the
+ * 16-B granule that holds the chunk's last byte (the 4-B granule for a page
+ * off the 16-B grid); pages may lie anywhere and repeat across contexts, and
+ * a context may own more entries than it reads.
+ * Routes, per group of 64 contexts (one wave):
+ *   loader  no context of the group that gets bytes has a pending partial
+ *           block ((bits[0] >> 3) & 63 == 0 wherever d_lens[i] > 0).  The
+ *           pages are walked as md5hip_digest_pages walks them -- LDS-DMA,
+ *           non-temporal when every page is on a 128-B line; a page index at
+ *           which some page is off the 16-B grid lane by lane -- from each
+ *           context's own buf.  Objects arriving in whole pages stay here:
+ *           only an object's last block leaves pending bytes.
+ *   lane    any other group: a pending block shifts every later 64-B block
+ *           64 - t bytes into the stream, one block a page then straddles two
+ *           pages, and an update of fewer than 64 - t bytes only appends.
+ *           Each context walks its own bytes -- correct, slower.
+ * A group's route is its own: a lane-route group does not slow the others of
+ * the launch.  A call over few contexts lasts one context's serial chain (no
+ * fed pairs here, unlike md5hip_update_ctx: DESIGN.md §5.9).
+ */
+int md5hip_update_ctx_pages(struct MD5Context *d_ctxs, const uint64_t *d_pages,
+                            const uint64_t *d_first, const uint32_t *d_lens, uint64_t n,
+                            uint32_t page_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,7 @@ def lib():
         "crc32hip_pages": (i, [vp, vp, vp, vp, u64, u32, u32, vp, vp]),
         "md5_batch_verify_device_pages": (i, [vp, vp, vp, vp, u64, u32, vp, vp, i, vp, i, vp, vp]),
         "md5_batch_upgrade_device_pages": (i, [vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, i, vp, vp]),
+        "md5hip_update_ctx_pages": (i, [vp, vp, vp, vp, u64, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -220,7 +221,7 @@ EXPORTS = ["MD5Init", "MD5Update", "MD5Final", "nc_MD5Init", "nc_MD5Update", "nc
            "md5hip_digest_compare", "md5hip_batch_verify_iov_async", "md5hip_batch_upgrade_iov_async",
            "md5_batch_verify_device", "md5hip_pool_verify_iov_async", "md5hip_pool_upgrade_iov_async",
            "md5hip_digest_pages", "md5_batch_submit_device_pages", "crc32hip_pages",
-           "md5_batch_verify_device_pages", "md5_batch_upgrade_device_pages"]
+           "md5_batch_verify_device_pages", "md5_batch_upgrade_device_pages", "md5hip_update_ctx_pages"]
 
 
 def check(fn, rc):

@@ -3,7 +3,8 @@
 // page table, each the device address of a page of page_bytes, as netcache
 // keeps a block (nc_page_ctrl_t lists).  The pages are hashed where they lie.
 // Also blk_make_crc's fastcrc windows over such lists (crc32hip_pages), of
-// which only the windows' bytes are read.
+// which only the windows' bytes are read, and MD5Update on caller-owned
+// contexts from such lists (md5hip_update_ctx_pages).
 // A translation unit of its own, linked after md5_kernels.o and md5_verify.o:
 // the hash kernels' code object stays the first gfx950 bundle of the library,
 // byte for byte.
@@ -302,6 +303,164 @@ crc32_pages_fast(PageBatch pb, uint64_t n, uint32_t F, uint32_t* __restrict__ ou
   }
 }
 
+// ---------------------------------------------------------------------------
+// MD5Update on caller-owned contexts over page lists (md5hip_update_ctx_pages):
+// context i takes chunk i of a paged batch as md5.c:169-215 takes a buffer,
+// all 88 bytes of it left as MD5Update leaves them (md5_kernels.h, "MD5Update
+// / MD5Final on caller-owned contexts").  One wave per 64 contexts, a context's
+// index its lane; a group takes one of two routes, wave-uniformly.
+//
+// Loader: no lane that gets bytes has any pending (t == 0 wherever len > 0).
+// The lanes' 64-B blocks are then the pages' own, and pages_group walks them
+// as it does for a digest -- LDS-DMA stages, a page index with a page off the
+// 16-B grid lane by lane -- from each lane's own buf[] and with nothing
+// appended (CtxHasher).  Across the walk a lane holds its state and what
+// pages_group holds; bits[] and in[] are read and built after it.
+//
+// Lane: some lane has pending bytes, so its blocks sit 64 - t bytes into the
+// stream and one a page straddles two pages.  Every lane walks its own byte
+// stream, block by block; a straddling block is put together from its two
+// pages byte by byte (put_bytes).  Correct, slower.
+// ---------------------------------------------------------------------------
+// pages_group's finish is handed where the walk ended -- the first byte after
+// the last whole block of the lane's last page -- and keeps it for the tail.
+struct CtxPagesHasher : CtxHasher {
+  const uint8_t* tail;
+  __device__ __forceinline__ void finish(State&, const uint8_t* t, uint32_t, uint64_t) { tail = t; }
+};
+
+__device__ __forceinline__ void block_words(uint32_t (&w)[16], const uint8_t* p) {
+  uint4 v[4];
+  if (((uintptr_t)p & 15u) == 0) load_block(v, reinterpret_cast<const uint4*>(p));
+  else load_block_unaligned(v, p);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    w[4 * k] = v[k].x; w[4 * k + 1] = v[k].y;
+    w[4 * k + 2] = v[k].z; w[4 * k + 3] = v[k].w;
+  }
+}
+
+// Word j of in[] as md5.c:214 leaves it: the r tail bytes (tw), then the bytes
+// of `keep` -- the last block compressed, or in[] as it was.
+__device__ __forceinline__ uint32_t in_word(uint32_t tw, uint32_t keep, uint32_t r, int j) {
+  const uint32_t m = tail_mask((int)r - 4 * j);
+  return (tw & m) | (keep & ~m);
+}
+
+// The lane route for one context with len > 0: buf and in[] of the context
+// at cp (the caller advances the bit count).  The stream position is (e, q):
+// byte q < P of the chunk's table entry e.  An entry is read only when a byte
+// of it is.
+__device__ __forceinline__ void ctx_pages_lane(uint32_t* __restrict__ cp, const PageBatch& pb, uint64_t pf,
+                                               uint32_t len, const CtxSpan& sp) {
+  const uint32_t P = pb.page_bytes;
+  auto page = [&](uint32_t e) __attribute__((always_inline)) {
+    return reinterpret_cast<const uint8_t*>((uintptr_t)pb.pages[pf + e]);
+  };
+  uint32_t keep[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) keep[j] = cp[6 + j];
+  if (sp.append_only) {                                // md5.c:189-192; t + len < 64 <= P: one page
+    put_bytes(keep, sp.t, page(0), len);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) cp[6 + j] = keep[j];
+    return;
+  }
+  State st{cp[0], cp[1], cp[2], cp[3]};
+  if (sp.t) {                                          // md5.c:194-199: complete the pending block
+    put_bytes(keep, sp.t, page(0), 64u - sp.t);
+    compress<true>(st, [&](int k) __attribute__((always_inline)) { return keep[k]; });
+  }
+  uint32_t e = 0, q = sp.pos;                          // pos < 64 <= P
+  uint32_t w[16];
+  for (uint32_t b = 0; b < sp.nblk; ++b) {
+    if (q + 64u <= P) {
+      block_words(w, page(e) + q);
+    } else {                                           // P - q bytes end page e, the rest start page e + 1
+#pragma unroll
+      for (int j = 0; j < 16; ++j) w[j] = 0u;
+      put_bytes(w, 0u, page(e) + q, P - q);
+      put_bytes(w, P - q, page(e + 1u), 64u - (P - q));
+    }
+    compress<true>(st, [&](int k) __attribute__((always_inline)) { return w[k]; });
+    q += 64u;
+    if (q >= P) {
+      q -= P;
+      ++e;
+    }
+  }
+  if (sp.nblk) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) keep[j] = w[j];
+  }
+  const uint32_t r = len - sp.pos - (sp.nblk << 6);    // md5.c:214: memcpy(in, buf, r)
+  uint32_t tw[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) tw[j] = 0u;
+  if (r) {
+    const uint32_t c1 = r < P - q ? r : P - q;
+    put_bytes(tw, 0u, page(e) + q, c1);
+    if (r > c1) put_bytes(tw, c1, page(e + 1u), r - c1);
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) cp[6 + j] = in_word(tw[j], keep[j], r, j);
+  cp[0] = st.a; cp[1] = st.b; cp[2] = st.c; cp[3] = st.d;
+}
+
+// One-wave workgroups with the loader's 8 KiB image, held at 4 waves per SIMD
+// by the register file, as md5_pages_xdma and md5_update_ctx.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
+md5_update_ctx_pages(uint32_t* __restrict__ ctxs, PageBatch pb, uint64_t n) {
+  __shared__ __attribute__((aligned(16))) uint8_t img[8192];
+  asm volatile("" ::: "v127");
+  const uint64_t first = (uint64_t)blockIdx.x * 64u;
+  if (first >= n) return;
+  const uint64_t i = first + (threadIdx.x & 63u);
+  const bool live = i < n;
+  uint32_t* cp = ctxs + 22 * (live ? i : first);
+  const uint32_t len = live ? pb.lens[i] : 0u;
+  const uint32_t t0 = cp[4];
+  const CtxSpan sp = ctx_span(t0, len);
+  const uint32_t lo = t0 + (len << 3);                 // md5.c:179-182
+  const uint32_t carry = (lo < t0 ? 1u : 0u) + (len >> 29);
+  if (__ballot(len != 0 && sp.t != 0) != 0) {          // wave-uniform: the lane route
+    if (len == 0) return;                              // no update: the context is not written
+    ctx_pages_lane(cp, pb, pb.first[i], len, sp);
+    cp[4] = lo;
+    cp[5] += carry;
+    return;
+  }
+  CtxPagesHasher h;
+  h.s0 = State{cp[0], cp[1], cp[2], cp[3]};
+  h.res = h.s0;
+  h.tail = nullptr;
+  pages_group(h, pb, n, first, static_cast<uint4*>(nullptr), img);
+  if (len == 0) return;
+  // t == 0: len >> 6 blocks were compressed, and len & 63 bytes are left at
+  // h.tail.  The last block compressed ends there, unless the last page holds
+  // fewer than 64 bytes (len = kP + 1 .. kP + 63): then it ends the page
+  // before, whose table entry is read a second time.
+  const uint32_t P = pb.page_bytes, r = len & 63u;
+  uint32_t keep[16];
+  if (len < 64u) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) keep[j] = cp[6 + j];
+  } else {
+    const uint32_t np = (uint32_t)(((uint64_t)len + P - 1u) / P);
+    const uint32_t lastb = len - (np - 1u) * P;        // the chunk's bytes in its last page
+    const uint8_t* blk = h.tail - 64;
+    if (lastb < 64u) blk = reinterpret_cast<const uint8_t*>((uintptr_t)pb.pages[pb.first[i] + np - 2u]) + (P - 64u);
+    block_words(keep, blk);
+  }
+  uint32_t tw[16];
+  load_tail(h.tail, r, tw);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) cp[6 + j] = in_word(tw[j], keep[j], r, j);
+  cp[0] = h.res.a; cp[1] = h.res.b; cp[2] = h.res.c; cp[3] = h.res.d;
+  cp[4] = lo;
+  cp[5] += carry;
+}
+
 template <typename... P, typename... A>
 int launch(void (*kern)(P...), uint64_t grid, uint32_t block, void* stream, A... args) {
   hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(block), 0, (hipStream_t)stream, static_cast<P>(args)...);
@@ -354,4 +513,17 @@ extern "C" int crc32hip_pages(const uint64_t* d_pages, const uint64_t* d_first, 
   const PageBatch pb{d_pages, d_first, d_lens, nullptr, page_bytes};
   const uint64_t cus = (uint64_t)md5hip_cu_count();
   return launch(crc32_pages_fast, groups < cus ? groups : cus, 1024, stream, pb, n, fastcrc, d_crcs);
+}
+
+extern "C" int md5hip_update_ctx_pages(struct MD5Context* d_ctxs, const uint64_t* d_pages, const uint64_t* d_first,
+                                       const uint32_t* d_lens, uint64_t n, uint32_t page_bytes, void* stream) {
+  if (n == 0) return 0;
+  const uint64_t groups = (n + 63) / 64;                 // one wave per 64 contexts
+  if (!d_ctxs || !d_pages || !d_first || !d_lens || ((uintptr_t)d_ctxs & 3u) || page_bytes == 0 ||
+      (page_bytes & 127u) || page_bytes > MD5HIP_PAGE_BYTES_MAX || groups > 0x7fffffffull)
+    return -EINVAL;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -ENODEV;
+  const PageBatch pb{d_pages, d_first, d_lens, nullptr, page_bytes};
+  return launch(md5_update_ctx_pages, groups, 64, stream, reinterpret_cast<uint32_t*>(d_ctxs), pb, n);
 }

@@ -252,6 +252,25 @@ def update_ctx(ctxs, ptrs, lens, stream=None):
     return ctxs
 
 
+def update_ctx_pages(ctxs, pages, first, lens, page_bytes: int, stream=None):
+    """md5hip_update_ctx_pages: MD5Update(ctx[i], chunk i, lens[i]) for every
+    i, chunk i laid out as a page list (digest_pages' arrays: byte k of it is
+    byte k % page_bytes of the page at pages[first[i] + k // page_bytes]) and
+    hashed where the pages lie.  ``pages`` and ``first`` are int64 device
+    tensors, ``lens`` int32, one entry of the last two per context."""
+    n = _ctx_tensor(ctxs)
+    for t, what in ((pages, "pages"), (first, "first"), (lens, "lens")):
+        _need_cuda(t, what)
+    if pages.dtype != torch.int64 or first.dtype != torch.int64 or lens.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("pages and first must be int64 and lens int32")
+    if lens.numel() != n or first.numel() < n:
+        raise ValueError("one first entry and one length per context")
+    check("md5hip_update_ctx_pages",
+          lib().md5hip_update_ctx_pages(ctxs.data_ptr(), pages.data_ptr(), first.data_ptr(), lens.data_ptr(),
+                                        n, page_bytes, _stream(stream)))
+    return ctxs
+
+
 def final_ctx(ctxs, out=None, stream=None):
     """MD5Final on every context: uint8 [n, 16] digests on the device; the
     contexts are zeroed (md5.c:264)."""
@@ -1150,7 +1169,7 @@ def pool_plan(lens, nparts: int) -> np.ndarray:
     return first
 
 
-__all__ = ["init_ctx", "update_ctx", "final_ctx", "MD5Context", "MD5Init", "MD5Update", "MD5Final", "MD5_DIGEST_SIZE", "MD5HipError", "arena_empty",
+__all__ = ["init_ctx", "update_ctx", "update_ctx_pages", "final_ctx", "MD5Context", "MD5Init", "MD5Update", "MD5Final", "MD5_DIGEST_SIZE", "MD5HipError", "arena_empty",
            "plan_desc", "plan_desc_at",
            "md5", "digest_fixed", "digest_desc", "digest_compare", "crc32_fixed", "crc32_desc", "md5crc32_fixed", "md5crc32_desc", "md5crc32_plan",
            "MD5CRC32_VARIANTS", "MD5CRC32_FEDSPLIT_MIN_LEN",
