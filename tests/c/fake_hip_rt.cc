@@ -1,6 +1,6 @@
 // fake_hip_rt.cc -- TEST INFRASTRUCTURE: a recording stand-in for the HIP
-// runtime, just the entries the host half of md5_kernels.o calls.  Linked
-// statically with the real object and md5_plan.o into tests/c/launch_check.cc
+// runtime, just the entries the host halves of md5_kernels.o and md5_pages.o
+// call.  Linked statically with the real objects and md5_plan.o into tests/c/launch_check.cc
 // (never preloaded, never loaded into Python), it lets the launchers of
 // sproxy_amd/csrc/md5_kernels.hip run on a machine without a GPU: no kernel
 // executes, every launch is written down.
@@ -66,8 +66,14 @@ std::string demangled(const char* mangled) {
 }
 
 // "void md5hip::md5_desc_fed<true>(unsigned char const*, ...)" -> "md5hip::md5_desc_fed<true>"
+// A kernel of an unnamed namespace (md5_pages.o's) loses that prefix, in its
+// template arguments too, before the parameter list is cut off at its "(":
+// "void (anonymous namespace)::pages_xdma16<(anonymous namespace)::md5hip::Crc32PermHasher>((anonymous ..."
+// -> "pages_xdma16<md5hip::Crc32PermHasher>"
 std::string short_name(const std::string& full) {
+  static const std::string anon = "(anonymous namespace)::";
   std::string s = full.compare(0, 5, "void ") == 0 ? full.substr(5) : full;
+  for (size_t at = s.find(anon); at != std::string::npos; at = s.find(anon, at)) s.erase(at, anon.size());
   const size_t paren = s.find('(');
   return paren == std::string::npos ? s : s.substr(0, paren);
 }
@@ -142,12 +148,21 @@ hipError_t hipLaunchKernel(const void* host_stub, dim3 grid, dim3 block, void** 
     abort();
   }
   std::string a;
-  for (int k = 0; k < la->nargs; ++k) {
+  auto field = [&a](const void* at, size_t size) {
     uint64_t v = 0;
-    memcpy(&v, args[k], la->size[k]);          // little-endian host: the low bytes
+    memcpy(&v, at, size);                      // little-endian host: the low bytes
     char buf[24];
-    snprintf(buf, sizeof buf, "%s0x%llx", k ? "," : "", (unsigned long long)v);
+    snprintf(buf, sizeof buf, "%s0x%llx", a.empty() ? "" : ",", (unsigned long long)v);
     a += buf;
+  };
+  for (int k = 0; k < la->nargs; ++k) {
+    if (la->size[k] == kPageBatch) {           // by value: four pointers and page_bytes
+      const char* pb = static_cast<const char*>(args[k]);
+      for (int f = 0; f < 4; ++f) field(pb + 8 * f, 8);
+      field(pb + 32, 4);
+    } else {
+      field(args[k], la->size[k]);
+    }
   }
   record("launch|%s|%u,%u,%u|%u,%u,%u|%zu|0x%llx|%s", name.c_str(), grid.x, grid.y, grid.z, block.x, block.y,
          block.z, lds, (unsigned long long)(uintptr_t)stream, a.c_str());

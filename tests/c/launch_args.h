@@ -2,11 +2,16 @@
 // without its template arguments (sproxy_amd/csrc/md5_kernels.h has the
 // signatures): hipLaunchKernel gets an array of pointers to the arguments and
 // no sizes, so the recording runtime (fake_hip_rt.cc) cuts them by this table.
-// A kernel that is not listed aborts the harness.  Test infrastructure.
+// A kernel that is not listed aborts the harness.  An argument of kPageBatch
+// bytes is md5_pages.hip's PageBatch, passed by value: it is recorded field by
+// field (pages, first, lens, order, page_bytes -- the 4 bytes of padding after
+// page_bytes are not).  Test infrastructure.
 #ifndef SPROXY_AMD_TESTS_LAUNCH_ARGS_H
 #define SPROXY_AMD_TESTS_LAUNCH_ARGS_H
 
 #include <string.h>
+
+enum { kPageBatch = 40 };    // sizeof(PageBatch): four pointers, a uint32_t, padding
 
 struct LaunchArgs {
   const char* kernel;
@@ -48,6 +53,12 @@ static const LaunchArgs kLaunchArgs[] = {
     // segs, nseg, dst / dst, n16, seed
     {"md5hip::gather_segments", 3, {8, 8, 8}},
     {"md5hip::fill_synthetic", 3, {8, 8, 8}},
+    // md5_pages.hip (an unnamed namespace, fake_hip_rt.cc's short_name): pb, n, out
+    {"md5_pages_xdma", 3, {kPageBatch, 8, 8}},
+    {"pages_xdma16", 3, {kPageBatch, 8, 8}},
+    // pb, n, F, out / ctxs, pb, n
+    {"crc32_pages_fast", 4, {kPageBatch, 8, 4, 8}},
+    {"md5_update_ctx_pages", 3, {8, kPageBatch, 8}},
 };
 
 // `name` may carry template arguments: "md5hip::md5_desc_fed<true>"

@@ -1,6 +1,6 @@
 // launch_check.cc -- TEST INFRASTRUCTURE: calls the real launchers of
-// sproxy_amd/csrc/md5_kernels.hip (build/obj/md5_kernels.o, with md5_plan.o)
-// over the recording runtime tests/c/fake_hip_rt.cc and prints what each call
+// sproxy_amd/csrc/md5_kernels.hip and md5_pages.hip (build/obj/md5_kernels.o
+// and md5_pages.o, with md5_plan.o) over the recording runtime tests/c/fake_hip_rt.cc and prints what each call
 // launched.  No GPU, no libamdhip64: no kernel runs, so the pointers are
 // whatever numbers the case gives (the launchers test them for NULL and
 // alignment and never read through them).
@@ -101,6 +101,22 @@ const Entry kEntries[] = {
     {"md5hip_init_ctx", 3, [](Args a) { return md5hip_init_ctx(ctxp(a[0]), a[1], ptr<void>(a[2])); }},
     {"md5hip_update_ctx", 5,
      [](Args a) { return md5hip_update_ctx(ctxp(a[0]), ptr<const void* const>(a[1]), u32p(a[2]), a[3], ptr<void>(a[4])); }},
+    // sproxy_amd/csrc/md5_pages.hip (build/obj/md5_pages.o)
+    {"md5hip_digest_pages", 9,
+     [](Args a) {
+       return md5hip_digest_pages((int)a[0], u64p(a[1]), u64p(a[2]), u32p(a[3]), u32p(a[4]), a[5], (uint32_t)a[6],
+                                  ptr<void>(a[7]), ptr<void>(a[8]));
+     }},
+    {"crc32hip_pages", 9,
+     [](Args a) {
+       return crc32hip_pages(u64p(a[0]), u64p(a[1]), u32p(a[2]), u32p(a[3]), a[4], (uint32_t)a[5], (uint32_t)a[6],
+                             ptr<uint32_t>(a[7]), ptr<void>(a[8]));
+     }},
+    {"md5hip_update_ctx_pages", 7,
+     [](Args a) {
+       return md5hip_update_ctx_pages(ctxp(a[0]), u64p(a[1]), u64p(a[2]), u32p(a[3]), a[4], (uint32_t)a[5],
+                                      ptr<void>(a[6]));
+     }},
     {"md5hip_final_ctx", 4,
      [](Args a) { return md5hip_final_ctx(ctxp(a[0]), a[1], ptr<unsigned char>(a[2]), ptr<void>(a[3])); }},
     {"md5hip_gather_launch", 4,

@@ -1,7 +1,10 @@
-"""What the gfx950 code object says of each kernel: the AMDGPU metadata note
-(llvm-readelf --notes) of the device ELF inside build/obj/md5_kernels.o or
-libmd5hip.so, by kernel name as the launch records spell it
-("md5hip::md5_desc_fed<true>").  Metadata only: nothing is disassembled.
+"""What the gfx950 code objects say of each kernel: the AMDGPU metadata notes
+(llvm-readelf --notes) of the device ELFs inside build/obj/md5_kernels.o and
+build/obj/md5_pages.o, by kernel name as the launch records spell it
+("md5hip::md5_desc_fed<true>"; md5_pages.o's kernels, of an unnamed namespace,
+without a prefix: "md5_pages_xdma").  md5_pages.o's code object also carries
+unreachable copies of md5_kernels.h's kernels under internal names; no launch
+names them, and they are not listed.  Metadata only: nothing is disassembled.
 Test infrastructure.
 
 (after `make -C tests/c launch_check`, which names the kernels)
@@ -21,6 +24,10 @@ import tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM_BIN = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin")
 OBJECT = os.path.join(REPO, "build", "obj", "md5_kernels.o")
+OBJECTS = (OBJECT, os.path.join(REPO, "build", "obj", "md5_pages.o"))
+# md5_pages.hip's kernels, as the launch records spell them (tests/launch_cases.py)
+PAGED = ("md5_pages_xdma", "pages_xdma16<md5hip::Crc32PermHasher>", "pages_xdma16<md5hip::Md5Crc32Hasher>",
+         "crc32_pages_fast", "md5_update_ctx_pages")
 GOLDEN = os.path.join(REPO, "tests", "golden", "kernel_resources.json")
 FIELDS = ("agpr_count", "vgpr_count", "sgpr_count", "sgpr_spill_count", "vgpr_spill_count",
           "private_segment_fixed_size", "group_segment_fixed_size", "max_flat_workgroup_size")
@@ -33,9 +40,23 @@ def compiler_version() -> str:
     return "; ".join(line.strip() for line in out.stdout.splitlines()[:2])
 
 
-def read(names: dict, path: str = OBJECT) -> dict:
-    """{kernel: {field: int}} for the kernels of the code object in `path` that
-    `names` ({mangled: name}, from `launch_check --kernels`) lists."""
+def ours(name: str) -> bool:
+    """The product's kernels among those an object registers (rocPRIM's are not)."""
+    return name.startswith("md5hip::") or name in PAGED
+
+
+def read(names: dict, paths=OBJECTS) -> dict:
+    """{kernel: {field: int}} for the kernels of the code objects in `paths`
+    that `names` ({mangled: name}, from `launch_check --kernels`) lists."""
+    out = {}
+    for path in paths:
+        part = read_object(names, path)
+        assert not set(part) & set(out), sorted(set(part) & set(out))
+        out.update(part)
+    return out
+
+
+def read_object(names: dict, path: str) -> dict:
     sys.path.insert(0, REPO)
     from sproxy_amd import _lib
     with tempfile.NamedTemporaryFile(suffix=".co") as f:
@@ -80,7 +101,7 @@ def golden() -> dict:
 
 if __name__ == "__main__":
     table = {k: v for k, v in read(kernel_names(os.path.join(REPO, "build", "c", "launch_check"))).items()
-             if k.startswith("md5hip::")}
+             if ours(k)}
     doc = {"compiler": compiler_version(),
            "kernels": {k: {"vgpr_count": v["vgpr_count"], "sgpr_spill_count": v["sgpr_spill_count"]}
                        for k, v in sorted(table.items())}}

@@ -1,4 +1,4 @@
-"""What each launcher of sproxy_amd/csrc/md5_kernels.hip must launch: the case
+"""What each launcher of sproxy_amd/csrc/md5_kernels.hip and md5_pages.hip must launch: the case
 table of tests/test_launch_routes.py (no device: the real launchers over a
 recording runtime) and tests/test_launch_routes_gpu.py (the same arguments on
 the device, results against hashlib and zlib).
@@ -17,8 +17,9 @@ The cases sit on both sides of every edge the launchers have: n = 0, each
 -EINVAL, base and stride on and off the 16-B grid, the stride where 32-bit
 offsets end (2^25), the group counts at CUs and CUs + 1, the two-block edge
 of the fed pairs, every named variant, the CRC ladder's windows and their
-sizes, 12, 16 and 128 chunks per CU, the grid caps, and the one-pass kind's
-three bounds.  Test infrastructure."""
+sizes, 12, 16 and 128 chunks per CU, the grid caps, the one-pass kind's three
+bounds, and the three paged entries' kinds, page sizes and group counts.  Test
+infrastructure."""
 
 EINVAL = -22
 MAXGRID = 2**31 - 1                      # a launch's grid limit: a batch that needs more is -EINVAL
@@ -51,9 +52,9 @@ def ceil_div(a, b):
 
 
 # ------------------------------------------------------------------ records
-def launch(kernel, grid, block, lds, stream, *args):
+def launch(kernel, grid, block, lds, stream, *args, ns="md5hip::"):
     a = ",".join(x if isinstance(x, str) else hex(x) for x in args)
-    return f"launch|md5hip::{kernel}|{grid},1,1|{block},1,1|{lds}|{hex(stream)}|{a}"
+    return f"launch|{ns}{kernel}|{grid},1,1|{block},1,1|{lds}|{hex(stream)}|{a}"
 
 
 class Case:
@@ -266,6 +267,60 @@ def route_blocks_of_256(kernel, n, ok, stream, *args):
     if not ok or ceil_div(n, 256) > MAXGRID:
         return EINVAL, [], None
     return 0, [launch(kernel, ceil_div(n, 256), 256, 0, stream, *args)], kernel
+
+
+# ---- page lists (md5_pages.hip).  Its kernels live in an unnamed namespace, and the records drop that
+# prefix (fake_hip_rt.cc), so their names carry no "md5hip::"; a PageBatch argument is recorded as its
+# five fields: pages, first, lens, order, page_bytes.
+DIGEST_MD5, DIGEST_CRC32, DIGEST_DUAL = 0, 1, 2              # enum md5hip_digest_kind
+PAGE_BYTES_MAX = 1 << 30                                     # MD5HIP_PAGE_BYTES_MAX
+PAGES_MD5, PAGES_CTX, PAGES_FAST = "md5_pages_xdma", "md5_update_ctx_pages", "crc32_pages_fast"
+PAGES_CRC, PAGES_DUAL = "pages_xdma16<md5hip::Crc32PermHasher>", "pages_xdma16<md5hip::Md5Crc32Hasher>"
+PAGED_KERNELS = (PAGES_MD5, PAGES_CRC, PAGES_DUAL, PAGES_FAST, PAGES_CTX)
+
+
+def page_bytes_ok(page_bytes):
+    """'page_bytes is a multiple of 128, at most MD5HIP_PAGE_BYTES_MAX'"""
+    return page_bytes != 0 and page_bytes % 128 == 0 and page_bytes <= PAGE_BYTES_MAX
+
+
+def route_digest_pages(cus, kind, pages, first, lens, order, n, page_bytes, out, stream):
+    if n == 0:                                              # 'n == 0: a no-op returning 0'
+        return 0, [], None
+    align = {DIGEST_MD5: 16, DIGEST_CRC32: 4, DIGEST_DUAL: 16}.get(kind)   # 'aligned to 16, 4 and 16'
+    groups = ceil_div(n, 64)
+    if (align is None or not pages or not first or not lens or not out or out % align
+            or not page_bytes_ok(page_bytes) or groups > MAXGRID):
+        return EINVAL, [], None
+    pb = (pages, first, lens, order, page_bytes)
+    if kind == DIGEST_MD5:                                  # one wave per workgroup, as md5_desc_xdma
+        return 0, [launch(PAGES_MD5, groups, 64, 0, stream, *pb, n, out, ns="")], PAGES_MD5
+    k = PAGES_CRC if kind == DIGEST_CRC32 else PAGES_DUAL   # 'one 768-thread workgroup per CU, grid-stride'
+    return 0, [launch(k, per_cu_grid(n, cus), 768, 0, stream, *pb, n, out, ns="")], k
+
+
+def route_crc_pages(cus, pages, first, lens, order, n, page_bytes, fastcrc, out, stream):
+    if fastcrc == 0:                                        # 'fastcrc == 0 IS md5hip_digest_pages(MD5HIP_DIGEST_CRC32, ..)'
+        return route_digest_pages(cus, DIGEST_CRC32, pages, first, lens, order, n, page_bytes, out, stream)
+    if n == 0:
+        return 0, [], None
+    groups = ceil_div(n, 32)                                # 64 window rows each
+    if (not pages or not first or not lens or not out or out % 4 or fastcrc % 4 or not page_bytes_ok(page_bytes)
+            or groups > MAXGRID):
+        return EINVAL, [], None
+    # 'every window has the same length, so d_order is not read': the kernel never gets it
+    return 0, [launch(PAGES_FAST, min(groups, cus), 1024, 0, stream, pages, first, lens, 0, page_bytes, n, fastcrc,
+                      out, ns="")], PAGES_FAST
+
+
+def route_update_ctx_pages(cus, ctxs, pages, first, lens, n, page_bytes, stream):
+    if n == 0:
+        return 0, [], None
+    groups = ceil_div(n, 64)                                # one wave per 64 contexts; 'There is no d_order'
+    if (not ctxs or not pages or not first or not lens or ctxs % 4 or not page_bytes_ok(page_bytes)
+            or groups > MAXGRID):
+        return EINVAL, [], None
+    return 0, [launch(PAGES_CTX, groups, 64, 0, stream, ctxs, pages, first, lens, 0, page_bytes, n, ns="")], PAGES_CTX
 
 
 # ------------------------------------------------------------------ the table
@@ -611,6 +666,89 @@ def cases(cus):
             if k == "fill_synthetic" else []
         add("fill." + id, "md5hip_fill_synthetic", [dst, nbytes, 0x5EED, STREAM],
             (EINVAL if k == EINVAL else 0, rec, None if k == EINVAL else k), k)
+
+    # ---- page lists: run on the device by tests/test_page_kinds.py and the paged test files
+    PAGED = "the paged kernels' results are checked by tests/test_page_kinds.py"
+    COUNTS = (1, 32, 33, 64, 65, 64 * cus, 64 * cus + 1)
+    KIND = {"md5": (DIGEST_MD5, PAGES_MD5), "crc32": (DIGEST_CRC32, PAGES_CRC), "md5crc32": (DIGEST_DUAL, PAGES_DUAL)}
+
+    def digest_pages(id, kind, n, kernel, pages=PTRS, first=OFFS, lens=LENS, order=ORDER, P=16384, out_=OUT,
+                     stream=STREAM):
+        route = route_digest_pages(cus, kind, pages, first, lens, order, n, P, out_, stream)
+        add("digest_pages." + id, "md5hip_digest_pages", [kind, pages, first, lens, order, n, P, out_, stream],
+            route, kernel, why=PAGED)
+
+    for name, (kind, k) in KIND.items():
+        for n in COUNTS:
+            digest_pages(f"{name}_n{n}", kind, n, k, P=(128, 384, 16384)[n % 3])
+        digest_pages(f"{name}_no_order", kind, 100, k, order=0)
+        digest_pages(f"{name}_empty", kind, 0, None, pages=0, first=0, lens=0, out_=0)
+        digest_pages(f"{name}_null_pages", kind, 64, EINVAL, pages=0)
+        digest_pages(f"{name}_null_first", kind, 64, EINVAL, first=0)
+        digest_pages(f"{name}_null_lens", kind, 64, EINVAL, lens=0)
+        digest_pages(f"{name}_null_out", kind, 64, EINVAL, out_=0)
+        for P in (0, 64, PAGE_BYTES_MAX + 128):
+            digest_pages(f"{name}_page_bytes_{P}", kind, 64, EINVAL, P=P)
+        digest_pages(f"{name}_page_bytes_max", kind, 64, k, P=PAGE_BYTES_MAX)
+        digest_pages(f"{name}_grid_limit", kind, 64 * MAXGRID, k)
+        digest_pages(f"{name}_grid_limit_plus_1", kind, 64 * MAXGRID + 1, EINVAL)
+        digest_pages(f"{name}_null_stream", kind, 65, k, stream=0)
+    digest_pages("md5_out_off_16", DIGEST_MD5, 64, EINVAL, out_=OUT + 8)
+    digest_pages("md5crc32_out_off_16", DIGEST_DUAL, 64, EINVAL, out_=OUT + 8)
+    digest_pages("crc32_out_off_4", DIGEST_CRC32, 64, EINVAL, out_=OUT + 2)
+    digest_pages("crc32_out_on_4", DIGEST_CRC32, 64, PAGES_CRC, out_=OUT + 4)
+    digest_pages("kind_3", 3, 64, EINVAL)
+    digest_pages("kind_minus_1", 2**32 - 1, 64, EINVAL)
+    digest_pages("kind_3_empty", 3, 0, None)                # n == 0 comes first
+
+    def crc_pages(id, n, F, kernel, pages=PTRS, first=OFFS, lens=LENS, order=ORDER, P=16384, out_=OUT):
+        route = route_crc_pages(cus, pages, first, lens, order, n, P, F, out_, STREAM)
+        add("crc_pages." + id, "crc32hip_pages", [pages, first, lens, order, n, P, F, out_, STREAM], route, kernel,
+            why=PAGED)
+
+    for n in COUNTS:
+        crc_pages(f"whole_n{n}", n, 0, PAGES_CRC)                       # the order goes through
+        crc_pages(f"window_64_n{n}", n, 64, PAGES_FAST, P=(128, 384, 16384)[n % 3])
+    for n in (32 * cus, 32 * cus + 1):                                  # ceil(n / 32) groups against the CUs
+        crc_pages(f"window_128_n{n}", n, 128, PAGES_FAST)
+    crc_pages("whole_no_order", 100, 0, PAGES_CRC, order=0)
+    crc_pages("window_no_order", 100, 128, PAGES_FAST, order=0)
+    for F in (4, 132, 1000, 1 << 20):                                   # any multiple of 4: one kernel
+        crc_pages(f"window_{F}", 100, F, PAGES_FAST)
+    for F in (0, 64):
+        crc_pages(f"empty_f{F}", 0, F, None, pages=0, first=0, lens=0, out_=0)
+        crc_pages(f"null_pages_f{F}", 64, F, EINVAL, pages=0)
+        crc_pages(f"null_first_f{F}", 64, F, EINVAL, first=0)
+        crc_pages(f"null_lens_f{F}", 64, F, EINVAL, lens=0)
+        crc_pages(f"null_out_f{F}", 64, F, EINVAL, out_=0)
+        crc_pages(f"out_off_4_f{F}", 64, F, EINVAL, out_=OUT + 2)
+        for P in (0, 64, PAGE_BYTES_MAX + 128):
+            crc_pages(f"page_bytes_{P}_f{F}", 64, F, EINVAL, P=P)
+    crc_pages("fastcrc_6", 64, 6, EINVAL)
+    crc_pages("fastcrc_130", 64, 130, EINVAL)
+    crc_pages("window_grid_limit", 32 * MAXGRID, 64, PAGES_FAST)
+    crc_pages("window_grid_limit_plus_1", 32 * MAXGRID + 1, 64, EINVAL)
+    crc_pages("whole_grid_limit_plus_1", 64 * MAXGRID + 1, 0, EINVAL)
+
+    def update_ctx_pages(id, n, kernel, ctxs=CTXS, pages=PTRS, first=OFFS, lens=LENS, P=16384, stream=STREAM):
+        route = route_update_ctx_pages(cus, ctxs, pages, first, lens, n, P, stream)
+        add("update_ctx_pages." + id, "md5hip_update_ctx_pages", [ctxs, pages, first, lens, n, P, stream], route,
+            kernel, why=PAGED)
+
+    for n in COUNTS:
+        update_ctx_pages(f"n{n}", n, PAGES_CTX, P=(128, 384, 16384)[n % 3])
+    update_ctx_pages("empty", 0, None, ctxs=0, pages=0, first=0, lens=0)
+    update_ctx_pages("null_ctxs", 64, EINVAL, ctxs=0)
+    update_ctx_pages("null_pages", 64, EINVAL, pages=0)
+    update_ctx_pages("null_first", 64, EINVAL, first=0)
+    update_ctx_pages("null_lens", 64, EINVAL, lens=0)
+    update_ctx_pages("ctxs_off_4", 64, EINVAL, ctxs=CTXS + 2)
+    for P in (0, 64, PAGE_BYTES_MAX + 128):
+        update_ctx_pages(f"page_bytes_{P}", 64, EINVAL, P=P)
+    update_ctx_pages("page_bytes_max", 64, PAGES_CTX, P=PAGE_BYTES_MAX)
+    update_ctx_pages("grid_limit", 64 * MAXGRID, PAGES_CTX)
+    update_ctx_pages("grid_limit_plus_1", 64 * MAXGRID + 1, EINVAL)
+    update_ctx_pages("null_stream", 65, PAGES_CTX, stream=0)
     return out
 
 
@@ -626,6 +764,9 @@ EXACT_BLOCK = {
     "md5hip::md5crc32_fedsplit<true>": 128, "md5hip::md5crc32_fedsplit<false>": 128,
     # four 8 KiB images for four waves; BALANCED's one wave per SIMD
     "md5hip::md5_fixed_xdma1nt": 256, "md5hip::md5_desc_balanced_t<4, 2, 2>": 256,
+    # md5_pages.hip: 'one wave per workgroup with its 8 KiB image'; 'XDMA16's frame ... twelve waves' images';
+    # 'crc32_fast_pipe's frame: the perm tables alone in LDS, sixteen waves per CU'
+    PAGES_MD5: 64, PAGES_CTX: 64, PAGES_CRC: 768, PAGES_DUAL: 768, PAGES_FAST: 1024,
 }
 LDS_PER_CU = 160 * 1024
 # workgroups a CU holds by LDS: (kernel, count, the comment it restates)
@@ -643,6 +784,9 @@ WORKGROUPS_PER_CU = [
     ("md5hip::crc32_fast_pipe", 2, "crc32_fast_pipe: the 16 table copies (64 KiB) of a 1,024-thread workgroup"),
     ("md5hip::md5crc32_fedsplit<true>", 2, "md5crc32_fedsplit: 'One 64 KiB LDS array ... so a CU holds two workgroups'"),
     ("md5hip::md5crc32_fedsplit<false>", 2, "md5crc32_fedsplit: 'One 64 KiB LDS array ... so a CU holds two workgroups'"),
+    (PAGES_FAST, 2, "crc32_pages_fast: 'the perm tables alone in LDS, sixteen waves per CU' (64 KiB a workgroup)"),
+    (PAGES_CRC, 1, "pages_xdma16: 'the 64 KiB tables beside twelve waves' images, one workgroup per CU'"),
+    (PAGES_DUAL, 1, "pages_xdma16: 'the 64 KiB tables beside twelve waves' images, one workgroup per CU'"),
 ]
 # waves per SIMD by registers: (kernel, 'eq' or 'ge', count, the comment it restates)
 WAVES_PER_SIMD = [
@@ -658,6 +802,11 @@ WAVES_PER_SIMD = [
      "md5crc32_fedsplit: '163 VGPRs ... and no AGPRs are three waves per SIMD'"),
     ("md5hip::md5crc32_fedsplit<false>", "eq", 3,
      "md5crc32_fedsplit: '163 VGPRs ... and no AGPRs are three waves per SIMD'"),
+    (PAGES_MD5, "eq", 4, "md5_pages_xdma: 'held at 4 waves per SIMD by the register file, as md5_desc_xdma'"),
+    (PAGES_CTX, "eq", 4, "md5_update_ctx_pages: 'held at 4 waves per SIMD by the register file'"),
+    (PAGES_FAST, "ge", 4, "crc32_pages_fast: 'VGPRs: 128 at 16 waves per CU' (four per SIMD)"),
+    (PAGES_CRC, "ge", 3, "pages_xdma16: XDMA16's frame, twelve waves per CU (three per SIMD)"),
+    (PAGES_DUAL, "ge", 3, "pages_xdma16: XDMA16's frame, twelve waves per CU (three per SIMD)"),
 ]
 
 

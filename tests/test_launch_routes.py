@@ -1,6 +1,7 @@
 """Which kernel a call runs, and with what geometry: the launchers of
-sproxy_amd/csrc/md5_kernels.hip with no device.  tests/c/launch_check.cc links
-the product's own build/obj/md5_kernels.o and md5_plan.o with a recording
+sproxy_amd/csrc/md5_kernels.hip and md5_pages.hip with no device.
+tests/c/launch_check.cc links the product's own build/obj/md5_kernels.o,
+md5_pages.o and md5_plan.o with a recording
 stand-in for the HIP runtime (tests/c/fake_hip_rt.cc) into a plain executable
 under ASan + UBSan -- nothing is preloaded, nothing is loaded into Python --
 and prints, for each case of tests/launch_cases.py, the return code and every
@@ -9,7 +10,7 @@ BALANCED's attribute call and memsets in order.  The table is run at 8, 256
 and 304 compute units, and its expectations are written from md5hip.h, never
 taken from the library.
 
-The same test reads the gfx950 code object's metadata notes (no disassembly)
+The same test reads the two gfx950 code objects' metadata notes (no disassembly)
 and holds the launches against them: no scratch and no VGPR spill in any
 kernel, every block within the kernel's limit and exactly the size its
 indexing is written for, LDS within a CU's 160 KiB, and the workgroups per CU
@@ -103,7 +104,7 @@ def _launches(observed):
 @pytest.fixture(scope="module")
 def resources(harness):
     table = kernel_resources.read(kernel_resources.kernel_names(harness))
-    return {k: v for k, v in table.items() if k.startswith("md5hip::")}
+    return {k: v for k, v in table.items() if kernel_resources.ours(k)}
 
 
 def test_the_table_reaches_every_kernel(observed, resources):
@@ -112,7 +113,7 @@ def test_the_table_reaches_every_kernel(observed, resources):
 
 
 def test_no_kernel_uses_scratch(resources):
-    assert len(resources) >= 29
+    assert len(resources) >= 34
     for k, r in resources.items():
         assert r["private_segment_fixed_size"] == 0, f"{k}: {r['private_segment_fixed_size']} B of scratch per lane"
         assert r["vgpr_spill_count"] == 0, f"{k}: {r['vgpr_spill_count']} VGPRs spilled"
@@ -130,7 +131,7 @@ def test_blocks_and_lds_fit_the_kernels(observed, resources):
     assert seen == set(lc.EXACT_BLOCK), sorted(set(lc.EXACT_BLOCK) - seen)
 
 
-@pytest.mark.parametrize("kernel,want,comment", lc.WORKGROUPS_PER_CU, ids=[r[0][8:] for r in lc.WORKGROUPS_PER_CU])
+@pytest.mark.parametrize("kernel,want,comment", lc.WORKGROUPS_PER_CU, ids=[r[0].removeprefix("md5hip::") for r in lc.WORKGROUPS_PER_CU])
 def test_workgroups_per_cu_by_lds(observed, resources, kernel, want, comment):
     dyns = {dyn for k, _, dyn in _launches(observed) if k == kernel}
     assert dyns, f"{kernel} never launched"
@@ -139,7 +140,7 @@ def test_workgroups_per_cu_by_lds(observed, resources, kernel, want, comment):
         assert lc.LDS_PER_CU // lds == want, f"{kernel}: {lds} B of LDS are {lc.LDS_PER_CU // lds} per CU; {comment}"
 
 
-@pytest.mark.parametrize("kernel,how,want,comment", lc.WAVES_PER_SIMD, ids=[r[0][8:] for r in lc.WAVES_PER_SIMD])
+@pytest.mark.parametrize("kernel,how,want,comment", lc.WAVES_PER_SIMD, ids=[r[0].removeprefix("md5hip::") for r in lc.WAVES_PER_SIMD])
 def test_waves_per_simd_by_registers(resources, kernel, how, want, comment):
     r = resources[kernel]
     got = lc.waves_per_simd(r["vgpr_count"], r["agpr_count"])
